@@ -18,7 +18,15 @@ Multi-GPU (one process per GPU, no data-path collective):
   (before any GPU call), each with RANK / LOCAL_RANK / WORLD_SIZE set; under torchrun, WORLD_SIZE must
   equal --gpus.
 
-Extra fields:
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the line
+(metric / value / unit / ms_per_step ...; the fields below are null or absent).  Every other measurement
+runs only under --full, after the timed region, each with its own --no-... switch.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (float32):
+pred_boxes (B, 4) cxcywh, pred_scores (B,) with the score head; with --train the step's loss statistics.
+Weights and frames are seeded, so two runs with the same arguments compute on identical inputs.
+
+Extra fields (--full):
   kernels        device time per launch of every plan entry inside the frame (inframe_profile: the
                  profiler's dispatch timestamps of graph-replayed frames, after the timed region)
   roofline       the kernel with the largest share of device time: algorithmic FLOPs per launch /
@@ -79,6 +87,25 @@ VARIANT_NAMES = {"rgbt": "mixformer_vit_rgbt (two-stream)", "shared": "mixformer
                  "asym_ce": "asymmetric_shared_ce (candidate elimination 3/6/9 x0.7)",
                  "rgb": "mixformer_vit (RGB-only, BASELINE config 1)"}
 GEO_RGB = {"hidden": 768, "depth": 12, "search": 288, "template": 128}  # config 1: MixViT-B 128/288
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32 (float64 stays float64).  An output larger than its
+    share of DUMP_BUDGET is reduced to a fixed sample of its flattened elements (seeded, sorted indices), the
+    same elements in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, v in arrays.items():
+        a = torch.as_tensor(v).detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def state_dict_keys(variant, hidden=768, depth=12, search=320, template=128, fusion_layers=2):
@@ -455,7 +482,7 @@ TRAIN_FLOP_PER_SAMPLE = 3 * 218.59e9  # forward + backward ~ 3
 
 
 def train_bench(world, rank, B, steps, warmup, device="cuda", ops=None, search=320, template=128, graph=True,
-                force_ddp=False):
+                force_ddp=False, dump=None):
     """BASELINE config 4: DDP training step of the two-stream MixViT-B RGB-T,
     B LaSOT-shaped synthetic pairs per GPU: forward with autograd on the HIP ops, CIoU + L1 box
     loss, backward with the RCCL gradient all-reduce (DistributedDataParallel, bucketed, overlapped
@@ -464,7 +491,8 @@ def train_bench(world, rank, B, steps, warmup, device="cuda", ops=None, search=3
     actors/mixformer_rgbt.py:33-168).  Returns the result object (samples/s over all ranks by the
     max-over-ranks time, ms per step, an MFMA roofline of the whole step).  device / ops / image sizes:
     the CPU harness test runs it over gloo with stand-in ops at small images (the product: HipOps).
-    force_ddp: the data-parallel step (bucketed all-reduce over the process group) even at world 1."""
+    force_ddp: the data-parallel step (bucketed all-reduce over the process group) even at world 1.
+    dump: directory for the last timed step's statistics (dump_outputs; rank 0)."""
     from mmt_amd.model import build_mixformer_vit_rgbt, hot_path_cfg
     from mmt_amd.train import HipOps, TrainStep, synthetic_batch
     torch.manual_seed(0)  # identical initial replicas (DDP also broadcasts rank 0's weights)
@@ -506,6 +534,8 @@ def train_bench(world, rank, B, steps, warmup, device="cuda", ops=None, search=3
         for i in range(warmup):
             step(i)
     elapsed = timed_steps(step, steps, world, sync, device)
+    if dump and rank == 0:
+        dump_outputs(dump, dict(last["stats"]))
     sps = world * B * steps / elapsed
     ach = sps / world * TRAIN_FLOP_PER_SAMPLE / 1e12  # per GPU
     # HBM bytes of one whole step from the committed counter pass (tools/pmc_train_traffic.py; one GPU, graphed
@@ -649,8 +679,14 @@ def resolve_world(gpus):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 20 with --train)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 20; 5 with --train)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (per-kernel profile and rooflines, "
+                         "batched MAM, K/V-cache / fp16 / tracking-loop rates, the training step, CPU baselines); "
+                         "the --no-... switches below drop single ones")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--batch", type=int, default=1, help="frames (sequences) per GPU per step")
     ap.add_argument("--variant", default="rgbt", choices=list(VARIANT_NAMES))
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "f32"],
@@ -688,10 +724,10 @@ def main():
     if args.train:
         if args.batch == 1:
             args.batch = 16  # yaml TRAIN.BATCH_SIZE
-        if args.steps == 200:
-            args.steps = 20
-        if args.warmup == 20:
-            args.warmup = 5
+    if args.steps is None:
+        args.steps = 20 if args.train else 200
+    if args.warmup is None:
+        args.warmup = 5 if args.train else 20
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # self-launch: one worker process per GPU
         sys.exit(launch_workers(args.gpus, sys.argv[1:]))
@@ -730,7 +766,7 @@ def main():
             plain = train_bench(1, 0, args.batch, args.steps, args.warmup, graph=not args.train_eager)
             torch.cuda.empty_cache()
         res = train_bench(world, rank, args.batch, args.steps, args.warmup, graph=not args.train_eager,
-                          force_ddp=args.force_ddp)
+                          force_ddp=args.force_ddp, dump=args.dump_outputs)
         if rank == 0:
             out = {"metric": "train samples/s (two-stream MixViT-B RGB-T DDP step, BASELINE config 4)",
                    "value": res["value"], "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -785,11 +821,17 @@ def main():
     elapsed = timed_steps(step, args.steps, world, torch.cuda.synchronize, "cuda")
 
     ws = rt.workspace(B)
+    if args.dump_outputs and rank == 0:  # what forward() returns: views of the workspace the last step wrote
+        outs = {"pred_boxes": ws["BOX"]}
+        if score:
+            outs["pred_scores"] = ws["SC"].view(-1)
+        dump_outputs(args.dump_outputs, outs)
     plan = ws["plan_score"] if score else ws["plan"]
     if args.dump_plan and rank == 0:
         with open(args.dump_plan, "w") as f:
             json.dump([e[2] for e in plan], f)
-    if args.no_kernel_profile:
+    full = args.full
+    if args.no_kernel_profile or not full:
         dom = mam = by = None
         dev_ms = span_ms = None
     else:
@@ -816,7 +858,7 @@ def main():
             "metric": METRIC, "value": round(frames / elapsed, 2), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
-            "dtype": args.dtype,
+            "dtype": args.dtype, "full": full,
             "data": "synthetic N(0,1) frames (seeded), seed-hash random-init weights (mmt-synth-v1)",
             "config": {"workload": "%s %s %dpx template x2 + %dpx search, %s, %s%s"
                                    % (VARIANT_NAMES[args.variant], "ViT-L" if args.vitl else "ViT-B", geo["template"],
@@ -836,19 +878,19 @@ def main():
                             "tflops": round(a["flops"] / a["n"] / (a["t"] / a["n"] * 1e-3) / 1e12, 1) if a["flops"] else None}
                         for k, a in sorted(by.items(), key=lambda kv: -kv[1]["t"])} if by else None,
         }
-        if args.dtype == "bf16" and not args.no_kernel_profile and not args.no_mam_batched:
+        if full and args.dtype == "bf16" and not args.no_kernel_profile and not args.no_mam_batched:
             out["roofline_mam_batched"] = mam_batched(rt)
             out["roofline_mam_batched_b8"] = mam_batched(rt, B=8)
-        if use_graph and not args.no_kv_cache and args.variant != "asym_ce":  # no template cache with CE
+        if full and use_graph and not args.no_kv_cache and args.variant != "asym_ce":  # no template cache with CE
             out["tracking_kv_cache"] = kv_cache_tracking(rt, pool, score, args.steps, args.warmup)
-        if use_graph and args.dtype == "bf16" and not args.no_fp16_line and args.variant != "asym_ce":
+        if full and use_graph and args.dtype == "bf16" and not args.no_fp16_line and args.variant != "asym_ce":
             out["fp16_line"] = fp16_line(sd, args.variant, pool, score, args.steps, args.warmup)
-        if use_graph and args.dtype == "bf16" and B == 1 and not args.no_tracker_line and not args.vitl:
+        if full and use_graph and args.dtype == "bf16" and B == 1 and not args.no_tracker_line and not args.vitl:
             try:
                 out["tracker_step"] = tracker_step(sd, args.variant, args.steps, args.warmup)
             except Exception as e:  # noqa: BLE001  (reported, not raised: the headline line must still print)
                 out["tracker_step"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if not args.no_train_line and args.variant == "rgbt" and not args.vitl and not sharded:
+    if full and not args.no_train_line and args.variant == "rgbt" and not args.vitl and not sharded:
         # config 4's DDP step beside the replicas: the one data-path collective (RCCL gradient
         # all-reduce) is timed at every N of a scaling run; a failure is reported, not raised
         del graphs, plans, pool
@@ -861,7 +903,7 @@ def main():
         train_res = None
     if rank == 0:
         out["train_step"] = train_res
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.variant, B, budget_s=20.0 if args.vitl else 12.0, geo=geo)
             if B == 1 and not args.vitl:  # BASELINE.md:58: B = 1 and B = 8
                 out["cpu_baseline_b8"] = cpu_baseline(args.variant, 8, budget_s=12.0, geo=geo)

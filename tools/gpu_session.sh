@@ -21,7 +21,7 @@ rc=$?
 echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 
-timeout -k 10 400 python bench.py "$@" > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python bench.py --full "$@" > "$OUT/bench.log" 2>&1
 rc=$?
 echo "bench rc=$rc"; tail -c 3000 "$OUT/bench.log"
 if [ $rc -ne 0 ]; then exit $rc; fi

@@ -11,9 +11,9 @@ run() {  # name, command...
   local rc=$?; echo "$name rc=$rc"; [ $rc -ne 0 ] && return $rc
   grep -h '^{' "$OUT/$name.log" | tail -1 >> "$OUT/configs.jsonl"
 }
-run rgb_fp16 python -u bench.py --variant rgb --dtype fp16 --no-cpu-baseline --no-mam-batched --no-kv-cache &&
-run shared64 python -u bench.py --variant shared --total-seqs 64 --no-cpu-baseline --no-kv-cache &&
-run vitl_fp16 python -u bench.py --vitl --variant asym_online --dtype fp16 --no-cpu-baseline --no-mam-batched --no-kv-cache &&
+run rgb_fp16 python -u bench.py --full --variant rgb --dtype fp16 --no-cpu-baseline --no-mam-batched --no-kv-cache &&
+run shared64 python -u bench.py --full --variant shared --total-seqs 64 --no-cpu-baseline --no-kv-cache &&
+run vitl_fp16 python -u bench.py --full --vitl --variant asym_online --dtype fp16 --no-cpu-baseline --no-mam-batched --no-kv-cache &&
 run train python -u tools/train_bench.py
 rc=$?
 cut -c1-200 "$OUT/configs.jsonl"

@@ -14,7 +14,7 @@ rc=$?; echo "smoke rc=$rc"; tail -1 "$OUT/smoke.log"; [ $rc -ne 0 ] && exit $rc
 fi
 timeout -k 10 300 python -u tools/attn_ab.py --impls 4,21,22,0 --batches 1,8,32 > "$OUT/attn_ab.jsonl" 2>&1
 rc=$?; echo "attn_ab rc=$rc"; grep -v amdgpu "$OUT/attn_ab.jsonl" | cut -c1-400; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python -u bench.py "$@" > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python -u bench.py --full "$@" > "$OUT/bench.log" 2>&1
 rc=$?; echo "bench rc=$rc"; grep -o '"value": [0-9.]*\|"roofline_mam[_a-z0-9]*": {"kernel": "mam_attention", "bound": "mfma", "achieved": [0-9.]*, "peak": [0-9.]*, "unit": "TFLOP/s", "frac": [0-9.]*' "$OUT/bench.log"; [ $rc -ne 0 ] && exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- \
