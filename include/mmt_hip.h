@@ -579,6 +579,37 @@ int mmt_batchnorm_relu_bwd(const void* x, const void* dy, void* dx, int64_t M, i
                            const float* save, int training, int relu, float* dgb, float* ws, int64_t ws_floats,
                            void* stream);
 
+/* SyncBatchNorm (nn.SyncBatchNorm -> nn.ReLU in training mode): the same maps and kernels with the batch
+ * statistics taken over every rank of a process group.  The caller issues the two collectives between the
+ * phases; everything exchanged is per channel and fp64 (8-byte aligned buffers).  relu / gamma / beta / pitch /
+ * save as above; every bad argument (also W < 1, a NULL or misaligned fp64 buffer, a short workspace) returns
+ * MMT_EBADARG before any launch; the library allocates nothing.
+ *   mmt_batchnorm_sync_stats: this rank's stats[3][C] = (mean, biased variance, count = M), mmt_batchnorm_relu's
+ *     sums and arithmetic kept in double.  (The sums are taken about a per-rank pivot, so ranks exchange
+ *     moments, not sums.)  ws: >= mmt_batchnorm_ws_floats(M, C) floats.
+ *   [all-gather of stats -> gathered[W][3][C], rank order]
+ *   mmt_batchnorm_sync_apply: folds the W triples per channel in rank order starting from rank 0's unchanged
+ *     (rank r: d = mean_r - mean, N = n + n_r, var = (n var + n_r var_r) / N + d^2 n n_r / N^2, mean += d n_r / N,
+ *     n = N), so every rank gets bitwise the same statistics and W = 1 reproduces mmt_batchnorm_relu bitwise;
+ *     then fp32 mean / variance, the running statistics update (momentum, unbiased variance on the global count
+ *     N), save, n_total[0] = N, and y.
+ *   mmt_batchnorm_sync_bwd_sums: against the global save, dgb fp32 [2][C] = this rank's (dgamma, dbeta) (local
+ *     sums, as torch's SyncBatchNorm returns them) and sums[2][C] = the same (sum g xhat, sum g) in double.
+ *     ws: >= mmt_batchnorm_ws_floats(M, C) floats.
+ *   [all-reduce (sum) of sums]
+ *   mmt_batchnorm_sync_bwd_dx: dx = gamma * invstd * (g - sum g / N - xhat * sum g xhat / N) with the reduced
+ *     sums and N = n_total[0] (divided in double).  ws: >= 3 C floats. */
+int mmt_batchnorm_sync_stats(const void* x, int64_t M, int C, int pitch, double* stats, float* ws, int64_t ws_floats,
+                             void* stream);
+int mmt_batchnorm_sync_apply(const void* x, void* y, int64_t M, int C, int pitch, const double* gathered, int W,
+                             const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             float momentum, float eps, int relu, float* save, double* n_total, void* stream);
+int mmt_batchnorm_sync_bwd_sums(const void* x, const void* dy, int64_t M, int C, int pitch, const float* save, int relu,
+                                float* dgb, double* sums, float* ws, int64_t ws_floats, void* stream);
+int mmt_batchnorm_sync_bwd_dx(const void* x, const void* dy, void* dx, int64_t M, int C, int pitch, const float* gamma,
+                              const float* save, const double* sums, const double* n_total, int relu, float* ws,
+                              int64_t ws_floats, void* stream);
+
 /* AdamW update with global-norm gradient clipping (torch.nn.utils.clip_grad_norm_
  * + torch.optim.AdamW's fused form over the reference's parameter groups, train_script_mixformer.py:
  * 105-140, base_functions.py:362-400).  Device tables: one entry per fp32 parameter tensor (p, its

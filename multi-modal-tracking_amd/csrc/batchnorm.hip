@@ -262,6 +262,87 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const u32x4* __re
     dx[i] = o;
 }
 
+// ---- SyncBatchNorm: batch statistics across the ranks of a process group.  The collectives run between the
+// launches (the caller's), so forward and backward split into phases; everything exchanged is per channel and
+// in double.
+
+// This rank's moments stats[3][C] = (mean, biased variance, count) from the pivoted partials: bn_finalize_kernel's
+// arithmetic and order, kept in double.  The pivot is this rank's own, so ranks exchange moments, never raw sums.
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_moments_kernel(const u32x4* __restrict__ x, const float* __restrict__ part,
+                                                                     int nblk, int64_t M, int C, double* __restrict__ stats) {
+    __shared__ double red[2 * BN_THREADS];
+    const int lane = threadIdx.x / BN_FCH, c = blockIdx.x * BN_FCH + threadIdx.x % BN_FCH;
+    double s = 0.0, q = 0.0;
+    bn_lane_sums(part, nblk, C, c, lane, red, s, q);
+    if (lane != 0 || c >= C) return;
+    const bf16_t* xb = (const bf16_t*)x;  // pivot: row 0
+    const double ms = s / (double)M;
+    const double vb = fmax(q / (double)M - ms * ms, 0.0);
+    stats[c] = (double)bf2f(xb[c]) + ms;
+    stats[C + c] = vb;
+    stats[2 * C + c] = (double)M;
+}
+
+// The ranks' moments g[W][3][C] folded per channel in rank order, starting from rank 0's triple unchanged (so every
+// rank computes the same bits, and W = 1 passes its values through); then bn_finalize_kernel's training branch on
+// the global count: fp32 mean / variance, the running statistics update, save[4][C].  n_total[0] = the global count.
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_fold_kernel(const double* __restrict__ g, int W, int C,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  float* running_mean, float* running_var, float momentum,
+                                                                  float eps, float* __restrict__ save, double* __restrict__ n_total) {
+    const int c = blockIdx.x * BN_THREADS + threadIdx.x;
+    if (c >= C) return;
+    double m = g[c], vb = g[C + c], n = g[2 * C + c];
+    for (int r = 1; r < W; ++r) {  // parallel-variance merge of rank r
+        const double* t = g + (int64_t)r * 3 * C;
+        const double mr = t[c], vr = t[C + c], nr = t[2 * C + c];
+        const double d = mr - m, N = n + nr;
+        vb = (n * vb + nr * vr) / N + d * d * n * nr / (N * N);
+        m += d * nr / N;
+        n = N;
+    }
+    const float mean = (float)m, var = (float)vb;
+    if (running_mean) {
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
+        const double vu = n > 1.0 ? vb * n / (n - 1.0) : vb;  // unbiased (running), global count
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)vu;
+    }
+    const float inv = 1.f / sqrtf(var + eps);
+    const float sc = (gamma ? gamma[c] : 1.f) * inv;
+    save[c] = mean;
+    save[C + c] = inv;
+    save[2 * C + c] = sc;
+    save[3 * C + c] = (beta ? beta[c] : 0.f) - mean * sc;
+    if (c == 0) n_total[0] = n;
+}
+
+// This rank's backward sums over the workgroups (bn_lane_sums order): dgb[2][C] = (dgamma, dbeta) in fp32 (local, as
+// torch's SyncBatchNorm leaves them) and the same two sums in double for the all-reduce
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_bwd_sums_kernel(const float* __restrict__ part, int nblk, int C,
+                                                                      float* __restrict__ dgb, double* __restrict__ sums) {
+    __shared__ double red[2 * BN_THREADS];
+    const int lane = threadIdx.x / BN_FCH, c = blockIdx.x * BN_FCH + threadIdx.x % BN_FCH;
+    double a, b;
+    bn_lane_sums(part, nblk, C, c, lane, red, a, b);
+    if (lane != 0 || c >= C) return;
+    dgb[c] = (float)a;
+    dgb[C + c] = (float)b;
+    sums[c] = a;
+    sums[C + c] = b;
+}
+
+// The dx coefficients from the reduced sums and the global count: coef[3][C] = (gamma * invstd, sum g / N, sum g xhat / N)
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_coef_kernel(const double* __restrict__ sums, const double* __restrict__ n_total,
+                                                                  int C, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ save, float* __restrict__ coef) {
+    const int c = blockIdx.x * BN_THREADS + threadIdx.x;
+    if (c >= C) return;
+    const double n = n_total[0];
+    coef[c] = (gamma ? gamma[c] : 1.f) * save[C + c];
+    coef[C + c] = (float)(sums[C + c] / n);
+    coef[2 * C + c] = (float)(sums[c] / n);
+}
+
 int bn_blocks(int64_t M) {  // ~32+ rows per workgroup, at most 256 workgroups (one per CU)
     const int64_t nb = (M + 31) / 32;
     return (int)(nb < 256 ? nb : 256);
@@ -309,5 +390,64 @@ extern "C" int mmt_batchnorm_relu_bwd(const void* x, const void* dy, void* dx, i
     const int64_t n8 = M * (pitch / 8);
     hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3((unsigned)((n8 + BN_THREADS - 1) / BN_THREADS)), dim3(BN_THREADS), 0, st,
                        (const u32x4*)x, (const u32x4*)dy, (u32x4*)dx, n8, C, pitch, save, (const float*)coef, relu);
+    return launch_status();
+}
+
+namespace {
+bool bn_f64_ok(const void* p) { return p && ((uintptr_t)p & 7) == 0; }
+}  // namespace
+
+extern "C" int mmt_batchnorm_sync_stats(const void* x, int64_t M, int C, int pitch, double* stats, float* ws,
+                                        int64_t ws_floats, void* stream) {
+    if (!bn_args_ok(x, M, C, pitch) || !bn_f64_ok(stats)) return MMT_EBADARG;
+    const int nb = bn_blocks(M);
+    if (!ws || ws_floats < (int64_t)nb * 2 * C) return MMT_EBADARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(nb), dim3(BN_THREADS), 0, st, (const u32x4*)x, M, C, pitch, ws);
+    hipLaunchKernelGGL(bn_sync_moments_kernel, dim3((C + BN_FCH - 1) / BN_FCH), dim3(BN_THREADS), 0, st, (const u32x4*)x,
+                       (const float*)ws, nb, M, C, stats);
+    return launch_status();
+}
+
+extern "C" int mmt_batchnorm_sync_apply(const void* x, void* y, int64_t M, int C, int pitch, const double* gathered, int W,
+                                        const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                        float momentum, float eps, int relu, float* save, double* n_total, void* stream) {
+    if (!bn_args_ok(x, M, C, pitch) || !y || ((uintptr_t)y & 15) || !save) return MMT_EBADARG;
+    if (W < 1 || !bn_f64_ok(gathered) || !bn_f64_ok(n_total)) return MMT_EBADARG;
+    if ((running_mean == nullptr) != (running_var == nullptr)) return MMT_EBADARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + BN_THREADS - 1) / BN_THREADS), dim3(BN_THREADS), 0, st, gathered, W, C,
+                       gamma, beta, running_mean, running_var, momentum, eps, save, n_total);
+    const int64_t n8 = M * (pitch / 8);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((n8 + BN_THREADS - 1) / BN_THREADS)), dim3(BN_THREADS), 0, st,
+                       (const u32x4*)x, (u32x4*)y, n8, C, pitch, (const float*)save, relu);
+    return launch_status();
+}
+
+extern "C" int mmt_batchnorm_sync_bwd_sums(const void* x, const void* dy, int64_t M, int C, int pitch, const float* save,
+                                           int relu, float* dgb, double* sums, float* ws, int64_t ws_floats, void* stream) {
+    if (!bn_args_ok(x, M, C, pitch) || !dy || ((uintptr_t)dy & 15) || !save || !dgb || !bn_f64_ok(sums)) return MMT_EBADARG;
+    const int nb = bn_blocks(M);
+    if (!ws || ws_floats < (int64_t)nb * 2 * C) return MMT_EBADARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(nb), dim3(BN_THREADS), 0, st, (const u32x4*)x, (const u32x4*)dy, M, C,
+                       pitch, save, relu, ws);
+    hipLaunchKernelGGL(bn_sync_bwd_sums_kernel, dim3((C + BN_FCH - 1) / BN_FCH), dim3(BN_THREADS), 0, st, (const float*)ws, nb,
+                       C, dgb, sums);
+    return launch_status();
+}
+
+extern "C" int mmt_batchnorm_sync_bwd_dx(const void* x, const void* dy, void* dx, int64_t M, int C, int pitch,
+                                         const float* gamma, const float* save, const double* sums, const double* n_total,
+                                         int relu, float* ws, int64_t ws_floats, void* stream) {
+    if (!bn_args_ok(x, M, C, pitch) || !dy || !dx || ((uintptr_t)dy & 15) || ((uintptr_t)dx & 15) || !save) return MMT_EBADARG;
+    if (!bn_f64_ok(sums) || !bn_f64_ok(n_total)) return MMT_EBADARG;
+    if (!ws || ws_floats < 3 * (int64_t)C) return MMT_EBADARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_sync_coef_kernel, dim3((C + BN_THREADS - 1) / BN_THREADS), dim3(BN_THREADS), 0, st, sums, n_total, C,
+                       gamma, save, ws);
+    const int64_t n8 = M * (pitch / 8);
+    hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3((unsigned)((n8 + BN_THREADS - 1) / BN_THREADS)), dim3(BN_THREADS), 0, st,
+                       (const u32x4*)x, (const u32x4*)dy, (u32x4*)dx, n8, C, pitch, save, (const float*)ws, relu);
     return launch_status();
 }

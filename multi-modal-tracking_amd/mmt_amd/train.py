@@ -707,6 +707,129 @@ class _HipBatchNormReLU(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None
 
 
+# A training-mode SyncBatchNorm's statistics over its process group on the HIP batch norm (sync_batchnorm_relu):
+# "auto": when the group has more than one rank (one rank: the local _HipBatchNormReLU, as before); "always": also
+# at one rank (tests, A/B); "off": the torch module on an NCHW copy, the path before the HIP phases existed
+SYNC_BN_COLLECTIVE = "auto"
+
+
+class HipBNPhases:
+    """The four phases of the cross-rank batch norm on the C ABI (mmt_batchnorm_sync_*), on NHWC bf16 maps of
+    `pitch` channels a row with C valid, launched on the current stream.  Every exchanged buffer is fp64."""
+
+    @staticmethod
+    def _dims(x):
+        if x.dtype != torch.bfloat16 or not x.is_contiguous():
+            raise ValueError("HIP batch norm: contiguous NHWC bf16 maps")
+        pitch = x.shape[-1]
+        return x.numel() // pitch, pitch
+
+    @staticmethod
+    def stats(x, C):
+        """-> this rank's [3][C] fp64 (mean, biased variance, count)."""
+        from ._lib import LIB, check
+        M, pitch = HipBNPhases._dims(x)
+        st = torch.empty(3, C, device=x.device, dtype=torch.float64)
+        nws = int(LIB.mmt_batchnorm_ws_floats(M, C))
+        ws = torch.empty(nws, device=x.device, dtype=torch.float32)
+        check(LIB.mmt_batchnorm_sync_stats(x.data_ptr(), M, C, pitch, st.data_ptr(), ws.data_ptr(), nws, _stream()),
+              "mmt_batchnorm_sync_stats")
+        return st
+
+    @staticmethod
+    def apply(x, C, gathered, W, weight, bias, running_mean, running_var, momentum, eps):
+        """gathered [W * 3][C] fp64 -> (y, save [4][C] fp32, n_total [1] fp64); the running statistics updated."""
+        from ._lib import LIB, check
+        M, pitch = HipBNPhases._dims(x)
+        y = torch.empty_like(x)
+        save = torch.empty(4, C, device=x.device, dtype=torch.float32)
+        n_total = torch.empty(1, device=x.device, dtype=torch.float64)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        check(LIB.mmt_batchnorm_sync_apply(x.data_ptr(), y.data_ptr(), M, C, pitch, gathered.data_ptr(), W, ptr(weight),
+                                           ptr(bias), ptr(running_mean), ptr(running_var), float(momentum), float(eps), 1,
+                                           save.data_ptr(), n_total.data_ptr(), _stream()), "mmt_batchnorm_sync_apply")
+        return y, save, n_total
+
+    @staticmethod
+    def bwd_sums(x, dy, C, save):
+        """-> (dgb [2][C] fp32: this rank's dgamma / dbeta, sums [2][C] fp64: the same, for the all-reduce)."""
+        from ._lib import LIB, check
+        M, pitch = HipBNPhases._dims(x)
+        dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
+        sums = torch.empty(2, C, device=x.device, dtype=torch.float64)
+        nws = int(LIB.mmt_batchnorm_ws_floats(M, C))
+        ws = torch.empty(nws, device=x.device, dtype=torch.float32)
+        check(LIB.mmt_batchnorm_sync_bwd_sums(x.data_ptr(), dy.data_ptr(), M, C, pitch, save.data_ptr(), 1, dgb.data_ptr(),
+                                              sums.data_ptr(), ws.data_ptr(), nws, _stream()), "mmt_batchnorm_sync_bwd_sums")
+        return dgb, sums
+
+    @staticmethod
+    def bwd_dx(x, dy, C, weight, save, sums, n_total):
+        """sums: reduced over the ranks -> dx."""
+        from ._lib import LIB, check
+        M, pitch = HipBNPhases._dims(x)
+        dx = torch.empty_like(x)
+        ws = torch.empty(3 * C, device=x.device, dtype=torch.float32)
+        check(LIB.mmt_batchnorm_sync_bwd_dx(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), M, C, pitch,
+                                            weight.data_ptr() if weight is not None else None, save.data_ptr(),
+                                            sums.data_ptr(), n_total.data_ptr(), 1, ws.data_ptr(), 3 * C, _stream()),
+              "mmt_batchnorm_sync_bwd_dx")
+        return dx
+
+
+class _SyncBatchNormReLU(torch.autograd.Function):
+    """nn.SyncBatchNorm (training) -> nn.ReLU on an NHWC map: the batch statistics over every rank of `group`.
+    Forward: phases.stats, all-gather of the [3][C] fp64 moments (mean, biased variance, count), phases.apply (the
+    ranks folded in rank order: bitwise the same statistics on every rank).  Backward: phases.bwd_sums, all-reduce of
+    the [2][C] fp64 (sum g xhat, sum g), phases.bwd_dx; dgamma / dbeta stay this rank's sums (DDP averages them, as
+    with torch's SyncBatchNorm).  Both collectives are synchronous calls on the current stream (a captured step
+    records them like the bucket all-reduces); no device value is read on the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, C, group, phases):
+        import torch.distributed as dist
+        W = dist.get_world_size(group)
+        stats = phases.stats(x, C)
+        # [W * 3][C], not [W][3][C]: gloo's all_gather_into_tensor takes the concatenated form only
+        gathered = torch.empty(W * 3, C, device=stats.device, dtype=stats.dtype)
+        dist.all_gather_into_tensor(gathered, stats, group=group)
+        y, save, n_total = phases.apply(x, C, gathered, W, weight, bias, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(x, weight, save, n_total)
+        ctx.C, ctx.group, ctx.phases = C, group, phases
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        import torch.distributed as dist
+        x, weight, save, n_total = ctx.saved_tensors
+        dy = dy.to(x.dtype).contiguous()
+        dgb, sums = ctx.phases.bwd_sums(x, dy, ctx.C, save)
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+        dx = ctx.phases.bwd_dx(x, dy, ctx.C, weight, save, sums, n_total)
+        dw = dgb[0] if ctx.needs_input_grad[1] else None
+        db = dgb[1] if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+def sync_batchnorm_relu(x, weight, bias, running_mean, running_var, momentum, eps, C, group=None, phases=HipBNPhases):
+    """SyncBatchNorm in training mode, then ReLU, on a contiguous NHWC map x [..][pitch] with C valid channels
+    (_SyncBatchNormReLU): statistics over every rank of `group` (None: the default group); running_mean /
+    running_var (or None) are updated in place with `momentum` and the unbiased variance on the global count.
+    phases: the backend of the four per-rank phases (HipBNPhases: the HIP kernels)."""
+    return _SyncBatchNormReLU.apply(x, weight, bias, running_mean, running_var, momentum, eps, C, group, phases)
+
+
+def _sync_bn_collective(bn):
+    """Whether a training SyncBatchNorm takes the cross-rank HIP path (SYNC_BN_COLLECTIVE)."""
+    if SYNC_BN_COLLECTIVE not in ("auto", "always", "off"):
+        raise ValueError("SYNC_BN_COLLECTIVE: 'auto', 'always' or 'off'")
+    import torch.distributed as dist
+    if (type(bn) is not torch.nn.SyncBatchNorm or not bn.training or SYNC_BN_COLLECTIVE == "off"
+            or not (dist.is_available() and dist.is_initialized())):
+        return False
+    return SYNC_BN_COLLECTIVE == "always" or dist.get_world_size(bn.process_group) > 1
+
+
 class _HipCornerScore(torch.autograd.Function):
     """One corner branch's score map in the training step (head.py:191-192): conv5 (Conv2d(48, 1, 1), in fp32 as
     HEAD_SCORE_FP32) + up4(adjust3) + up2(adjust4) -> (B, fh*fh) fp32, forward and backward on
@@ -1353,7 +1476,8 @@ class HipOps:
     def bn_relu(x, bn):
         """bn (nn.BatchNorm2d) then ReLU on an NHWC bf16 map (_HipBatchNormReLU), with the module's training /
         eval semantics: batch statistics when training or not tracking, running statistics updated (and
-        num_batches_tracked advanced) when training and tracking."""
+        num_batches_tracked advanced) when training and tracking.  A training nn.SyncBatchNorm in a process group
+        of more than one rank takes its statistics over the group (sync_batchnorm_relu; SYNC_BN_COLLECTIVE)."""
         if isinstance(bn, FrozenBatchNorm2d):  # fixed statistics and affine (buffers): eval semantics
             C = bn.weight.shape[0]
             x = x.to(torch.bfloat16)
@@ -1376,6 +1500,10 @@ class HipOps:
         padded = x.shape[-1] != C  # 8-channel rows in (a keep_pad conv): padded rows out, padding channels 0
         if not padded and C % 8:  # the 1-channel maps: 8-channel rows, padding channels ignored (autograd slices dy back)
             x = F.pad(x, (0, (C + 7) // 8 * 8 - C))
+        if _sync_bn_collective(bn):  # training SyncBatchNorm: statistics over its process group (or the default one)
+            y = sync_batchnorm_relu(x.contiguous(), bn.weight, bn.bias, bn.running_mean if keep else None,
+                                    bn.running_var if keep else None, bn.momentum, bn.eps, C, bn.process_group)
+            return y if (padded or y.shape[-1] == C) else y[..., :C]
         y = _HipBatchNormReLU.apply(x.contiguous(), bn.weight, bn.bias, bn.running_mean if keep else None,
                                     bn.running_var if keep else None, bn.momentum, bn.eps, training, C)
         return y if (padded or y.shape[-1] == C) else y[..., :C]
@@ -1770,9 +1898,10 @@ def _soft_argmax(score_map, stride):
 
 def _hip_bn_ok(bn):
     """The conv() block norms the HIP batch norm computes with the module's own semantics: BatchNorm2d with a
-    momentum, SyncBatchNorm when its statistics are local (eval, or a process group of one rank: SyncBatchNorm
-    then runs F.batch_norm itself), and FrozenBatchNorm2d (fixed statistics and affine, lib/models/mixformer_cvt/
-    utils.py:21-57)."""
+    momentum, SyncBatchNorm with a momentum -- local statistics in eval or in a process group of one rank
+    (SyncBatchNorm then runs F.batch_norm itself), statistics over the group's ranks in training otherwise
+    (sync_batchnorm_relu), unless SYNC_BN_COLLECTIVE is "off" -- and FrozenBatchNorm2d (fixed statistics and affine,
+    lib/models/mixformer_cvt/utils.py:21-57)."""
     if isinstance(bn, FrozenBatchNorm2d):
         return True
     if type(bn) is torch.nn.SyncBatchNorm:
@@ -1782,7 +1911,9 @@ def _hip_bn_ok(bn):
             return True
         import torch.distributed as dist
         pg = bn.process_group
-        return not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(pg) == 1
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(pg) == 1:
+            return True
+        return SYNC_BN_COLLECTIVE != "off"
     return type(bn) is torch.nn.BatchNorm2d and bn.momentum is not None
 
 
@@ -1808,8 +1939,9 @@ def head_forward_nhwc(hd, x, ops):
 def _head_forward_nhwc(hd, x, ops):
     """head_forward with NHWC maps and the 3x3 convolutions on ops.conv3x3 (HIP): every conv() block =
     conv (HIP) -> BatchNorm2d + ReLU on ops.bn_relu (HIP, the module's statistics semantics and running-stat
-    updates); SyncBatchNorm (its RCCL statistics), FrozenBatchNorm2d and the 1-channel maps call the modules
-    on the NCHW map as the reference runs them.  Nearest upsampling, the pyramid adds, the 48 -> 1 1x1 convs
+    updates; a training SyncBatchNorm's statistics over its process group through sync_batchnorm_relu); only a
+    cumulative-average norm (momentum None), or SyncBatchNorm with SYNC_BN_COLLECTIVE = "off", calls the module
+    on the NCHW map as the reference runs it.  Nearest upsampling, the pyramid adds, the 48 -> 1 1x1 convs
     and the soft-argmax stay PyTorch ops (head.py:147-212)."""
     nchw = lambda t: t.permute(0, 3, 1, 2)  # noqa: E731
     nhwc = lambda t: t.permute(0, 2, 3, 1)  # noqa: E731
@@ -1827,9 +1959,10 @@ def _head_forward_nhwc(hd, x, ops):
         bn = seq[1]
         if bn_relu is not None and type(seq[2]) is torch.nn.ReLU and _hip_bn_ok(bn):
             return bn_relu(y, bn)  # HIP batch norm + ReLU on the NHWC map
-        # SyncBatchNorm in a process group of more than one rank (its RCCL statistics) and cumulative-average
-        # BatchNorm (momentum None): the module on a contiguous NCHW map as the reference runs it (MIOpen's
-        # batch norm on the channels-last view of a bf16 map crashed in train mode: DESIGN.md §7)
+        # cumulative-average BatchNorm (momentum None), and SyncBatchNorm in a process group of more than one rank
+        # with SYNC_BN_COLLECTIVE = "off" (torch's own exchange): the module on a contiguous NCHW map as the
+        # reference runs it (MIOpen's batch norm on the channels-last view of a bf16 map crashed in train mode:
+        # DESIGN.md §7)
         return nhwc(seq[2](bn(nchw(y).contiguous()))).contiguous()
 
     def c1(mod, t):  # Conv2d(48, 1, 1) on channels-last rows
@@ -2127,6 +2260,17 @@ class GradBucketAllReduce:
             h.remove()
 
 
+def graph_capture_mode(collectives):
+    """The capture_error_mode for torch.cuda.graph; with `collectives` (the captured work issues process-group
+    collectives: TrainStep.capture explains why) the device is drained and the process group's watchdog given a
+    few polls first, and the mode is "thread_local"."""
+    if not collectives:
+        return "global"
+    torch.cuda.synchronize()
+    time.sleep(0.5)
+    return "thread_local"
+
+
 class TrainStep:
     """One optimisation step: forward, loss, backward, (data-parallel gradient all-reduce), clip, AdamW.
 
@@ -2240,11 +2384,7 @@ class TrainStep:
         # (every ~100 ms), and a query of such a work's event once the process group's stream has joined the
         # capture fails the same way (hipErrorCapturedEvent, seen once in the one-rank test): the device is
         # drained and the watchdog given a few polls to retire them before the capture starts.
-        mode = "global"
-        if self.reducer is not None:
-            torch.cuda.synchronize()
-            time.sleep(0.5)
-            mode = "thread_local"
+        mode = graph_capture_mode(self.reducer is not None)
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.graph_stats = self(t, o, s, gt_xywh)
         self.static_inputs = (t, o, s, gt_xywh)
