@@ -42,6 +42,8 @@
  *   mmt_spm_attention           ScoreDecoder single-query attention, score_decoder.py:55-61
  *   mmt_ce_t2s_attention / mmt_ce_select / mmt_ce_gather / mmt_ce_recover  candidate elimination
  *       of asymmetric_shared_ce.py:22-102, :198-202, :426-447 (attn_t2s mean, sorted top-k, recover)
+ *   mmt_ce_rows_gather / mmt_ce_index_invert  the same elimination under autograd (training): pruning, recovery and
+ *       their backwards as one indexed row copy of the packed fp32 stream
  *   mmt_sample_target           the trackers' host crop + preprocessing, processing_utils.py:15-77,
  *       tracker_utils.py:24-48 (cv2 crop/pad/resize, colour map, normalise)
  *   mmt_track_update            map_box_back + clip_box, lib/test/tracker/mixformer_vit_rgbt.py:92-95,
@@ -351,7 +353,15 @@ int mmt_ms_deform_attn_backward_impl(const void* value, const int64_t* spatial_s
  *   mmt_ce_gather: xc rows [0, n_t + keep) of every sequence = x's template rows then the kept
  *     rows in order (xn, if not NULL, gets the same rows cast to xn_dtype);
  *   mmt_ce_recover: out rows [n_t, n_t + ns_full) = x's surviving rows (slots [0, keep) of the
- *     final gidx) at their original positions, zeros where pruned (dtype MMT_BF16 / MMT_F32). */
+ *     final gidx) at their original positions, zeros where pruned (dtype MMT_BF16 / MMT_F32);
+ * and, for the training forward (packed fp32 streams [S][n_t + lens][C] that shrink at every stage):
+ *   mmt_ce_rows_gather: dst[s][r] = src[s][idx[s][r]] for fp32 rows of C values (C % 4 == 0, C <= 1024;
+ *     src [S][src_rows][C], dst [S][dst_rows][C], idx [S][dst_rows]); an index outside [0, src_rows) gives
+ *     a zero row and is never dereferenced; every destination row is written.  The pruning, the recovery
+ *     and both of their backwards are this call with four index vectors;
+ *   mmt_ce_index_invert: idx_out[s][idx_in[s][j]] = j for j < n_in, -1 elsewhere (idx_in [S][n_in],
+ *     idx_out [S][n_out], n_out <= 2048; entries outside [0, n_out) are skipped; deterministic for
+ *     distinct entries). */
 int mmt_ce_t2s_attention(const void* qkv, float* partial, int Bm, int tok_pitch, int n_t, int n_s, int C, int H,
                          float scale, int dtype, void* stream);
 int mmt_ce_t2s_attention_masked(const void* qkv, float* partial, const unsigned char* template_mask, int Bm,
@@ -362,6 +372,9 @@ int mmt_ce_gather(const float* x, float* xc, void* xn, const int* order, int S, 
                   int ns_full, int C, int xn_dtype, void* stream);
 int mmt_ce_recover(const float* x, const int* gidx, int keep, void* out, int S, int tok_pitch, int n_t, int ns_full,
                    int C, int dtype, void* stream);
+int mmt_ce_rows_gather(const float* src, int src_rows, float* dst, int dst_rows, const int* idx, int S, int C,
+                       void* stream);
+int mmt_ce_index_invert(const int* idx_in, int n_in, int* idx_out, int n_out, int S, void* stream);
 
 /* Bimodal encoder layer core (ms_deform_attn_bimodal.py:97-128) for nq queries per modality on an
  * hw x hw map, 8 heads x 64 ch, 2 levels x 4 points: offw[b*nq+q][192] fp32 = [sampling_offsets

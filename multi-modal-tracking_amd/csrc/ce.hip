@@ -31,6 +31,13 @@
 //                         LayerNorm GEMMs read)
 //   mmt_ce_recover        the backbone output's search rows at their original positions (zeros
 //                         where pruned), in the dtype the fusion reads
+//
+// Training (mmt_amd/train.py, autograd): the fp32 stream is packed [S][n_t + lens][C] and shrinks at
+// every stage, so pruning, its backward, the recovery and its backward are one operation with four
+// index vectors -- destination row r of sequence s is source row idx[s][r], or a zero row:
+//   mmt_ce_rows_gather    fp32 rows src [S][src_rows][C] -> dst [S][dst_rows][C] by idx [S][dst_rows]
+//                         (an index outside [0, src_rows) is a zero row and is never dereferenced)
+//   mmt_ce_index_invert   idx_out[s][idx_in[s][j]] = j, -1 elsewhere: the backward's index vector
 #include "common.hpp"
 
 namespace {
@@ -365,6 +372,51 @@ __global__ __launch_bounds__(256) void ce_recover_kernel(const float* __restrict
     }
 }
 
+// One wave per destination row, 4 rows per workgroup: the row's index is wave-uniform, every lane
+// moves up to 4 float4 (C <= 1024), all loads issued before the stores.  Every destination row is
+// written (zeros for idx outside [0, src_rows)), so dst needs no memset.
+constexpr int CE_RG_ROWS = 4, CE_RG_V = 4;
+__global__ __launch_bounds__(64 * CE_RG_ROWS) void ce_rows_gather_kernel(const float* __restrict__ src, int src_rows,
+                                                                         float* __restrict__ dst, int dst_rows,
+                                                                         const int* __restrict__ idx, int C4) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * CE_RG_ROWS + (threadIdx.x >> 6), s = blockIdx.y;
+    if (r >= dst_rows) return;
+    const int j = idx[(int64_t)s * dst_rows + r];
+    const bool live = j >= 0 && j < src_rows;
+    const float4* sp = (const float4*)src + ((int64_t)s * src_rows + (live ? j : 0)) * C4;
+    float4* dp = (float4*)dst + ((int64_t)s * dst_rows + r) * C4;
+    float4 v[CE_RG_V];
+#pragma unroll
+    for (int i = 0; i < CE_RG_V; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live && c < C4) v[i] = sp[c];
+    }
+#pragma unroll
+    for (int i = 0; i < CE_RG_V; ++i) {
+        const int c = lane + 64 * i;
+        if (c < C4) dp[c] = v[i];
+    }
+}
+
+// One workgroup per sequence: the inverse staged in LDS (n_out <= CE_MAXINV), filled with -1, then
+// slot j written at inv[idx_in[j]] (entries outside [0, n_out) skipped; distinct entries: one writer
+// per word, no atomics), then copied out whole.
+constexpr int CE_MAXINV = 2048;
+__global__ __launch_bounds__(256) void ce_index_invert_kernel(const int* __restrict__ idx_in, int n_in,
+                                                              int* __restrict__ idx_out, int n_out) {
+    __shared__ int inv[CE_MAXINV];
+    const int s = blockIdx.x;
+    for (int j = threadIdx.x; j < n_out; j += 256) inv[j] = -1;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n_in; j += 256) {
+        const int t = idx_in[(int64_t)s * n_in + j];
+        if (t >= 0 && t < n_out) inv[t] = j;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n_out; j += 256) idx_out[(int64_t)s * n_out + j] = inv[j];
+}
+
 }  // namespace
 
 extern "C" int mmt_ce_t2s_attention_masked(const void* qkv, float* partial, const unsigned char* template_mask, int Bm,
@@ -436,5 +488,23 @@ extern "C" int mmt_ce_recover(const float* x, const int* gidx, int keep, void* o
         hipLaunchKernelGGL(ce_recover_kernel<float>, grid, dim3(256), 0, st, x, gidx, keep, (float*)out, tok_pitch, n_t,
                            ns_full, C);
     else return MMT_EBADARG;
+    return launch_status();
+}
+
+extern "C" int mmt_ce_rows_gather(const float* src, int src_rows, float* dst, int dst_rows, const int* idx, int S, int C,
+                                  void* stream) {
+    if (!src || !dst || !idx || src == dst || S <= 0 || S > 65535 || src_rows <= 0 || dst_rows <= 0 || C <= 0 || C % 4 ||
+        C > 256 * CE_RG_V)
+        return MMT_EBADARG;
+    hipLaunchKernelGGL(ce_rows_gather_kernel, dim3((unsigned)((dst_rows + CE_RG_ROWS - 1) / CE_RG_ROWS), (unsigned)S),
+                       dim3(64 * CE_RG_ROWS), 0, (hipStream_t)stream, src, src_rows, dst, dst_rows, idx, C / 4);
+    return launch_status();
+}
+
+extern "C" int mmt_ce_index_invert(const int* idx_in, int n_in, int* idx_out, int n_out, int S, void* stream) {
+    if (!idx_in || !idx_out || idx_in == idx_out || S <= 0 || n_in <= 0 || n_out <= 0 || n_out > CE_MAXINV)
+        return MMT_EBADARG;
+    hipLaunchKernelGGL(ce_index_invert_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, idx_in, n_in,
+                       idx_out, n_out);
     return launch_status();
 }

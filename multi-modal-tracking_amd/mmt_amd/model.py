@@ -261,7 +261,8 @@ class _HipTracker(nn.Module):
                 self._rt = MixFormerRGBTRuntime(sd, self.variant, dtype=self.compute_dtype, device=device)
         return self._rt
 
-    def forward(self, template, online_template, search, run_score_head=False, gt_bboxes=None, return_features=False):
+    def forward(self, template, online_template, search, run_score_head=False, gt_bboxes=None, return_features=False,
+                **train_kw):
         for nm, x in (("template", template), ("online_template", online_template), ("search", search)):
             if not isinstance(x, (list, tuple)) or len(x) != 2:
                 raise ValueError("%s must be a list [rgb, tir] of (B,3,H,W) tensors" % nm)
@@ -275,7 +276,9 @@ class _HipTracker(nn.Module):
                 raise RuntimeError("the MI355X forward needs the inputs on the HIP device (got %s); there is no CPU path"
                                    % dev)
             return module_forward(self, template, online_template, search, ops, run_score_head=run_score_head,
-                                  gt_bboxes=gt_bboxes)
+                                  gt_bboxes=gt_bboxes, **train_kw)
+        if train_kw:
+            raise TypeError("unexpected arguments %s" % sorted(train_kw))
         if dev.type != "cuda":
             raise RuntimeError("the MI355X forward needs the inputs on the HIP device (got %s); there is no CPU path" % dev)
         rt = self._runtime(dev)
@@ -390,6 +393,8 @@ class MixFormer_RGBT_CE(MixFormer_RGBT_Shared):
                                                 device=device, ce=(self.ce_loc, keep), ce_mask_count=self._mask_count)
         return self._rt
 
+    ce_forced = None  # test hooks of the training forward (mmt_amd.train.backbone_forward_stacked), like train_ops
+    ce_trace = None
     _keep_override = None
     _mask_count = None  # template queries per frame the CE mean averages (None: all of them)
     _mask = None
@@ -404,9 +409,6 @@ class MixFormer_RGBT_CE(MixFormer_RGBT_Shared):
         (actors/mixformer_rgbt.py:67-90): the elimination then averages the template->search attention
         over the masked template queries only (candidate_elimination :81-89).  As in the reference
         (attn[mask].view(bs, hn, -1, ...)) every frame must select the same number of queries."""
-        if self.training and torch.is_grad_enabled():
-            raise NotImplementedError("training forward of asymmetric_shared_ce (candidate elimination with autograd) "
-                                      "is not built; its inference forward runs under eval() / no_grad()")
         count = None
         if ce_template_mask is not None:
             m = torch.as_tensor(ce_template_mask).to(torch.bool)
@@ -422,6 +424,12 @@ class MixFormer_RGBT_CE(MixFormer_RGBT_Shared):
             if count is not None:
                 ce_template_mask = m
         rate = None if ce_keep_rate is None else float(ce_keep_rate)
+        if self.training and torch.is_grad_enabled():
+            # training (the actor's call, actors/mixformer_rgbt.py:67-90): autograd through the elimination
+            # (mmt_amd.train.backbone_forward_stacked); an all-true mask is no mask
+            return super().forward(template, online_template, search, run_score_head=run_score_head,
+                                   gt_bboxes=gt_bboxes, ce_template_mask=ce_template_mask if count is not None else None,
+                                   ce_keep_rate=rate)
         if rate != self._keep_override or count != self._mask_count:
             self._keep_override = rate
             self._mask_count = count

@@ -12,12 +12,21 @@ ones carry `register_autograd` formulas built from the registered backward ops:
                                                 mmt_prroi_pool_* (fp32; prroi_pool/functional.py:38-76)
   mmt::mam_attention_forward / _backward        mmt_mam_attention (with log-sum-exp) / mmt_mam_attention_bwd
                                                 (bf16, the training form of mixformer.py:52-78)
+  mmt::ce_select                                mmt_ce_t2s_attention_masked + mmt_ce_select: the candidate
+                                                elimination's scores and sorted top-k (no autograd formula:
+                                                only indices leave get_token_from_attn,
+                                                asymmetric_shared_ce.py:22-46)
+  mmt::ce_rows_gather / mmt::ce_index_invert    mmt_ce_rows_gather / mmt_ce_index_invert: the pruning and the
+                                                recovery of the fp32 token rows in training; the backward of a
+                                                row gather is the row gather by the inverted index
 
 Each *_forward op has its backward registered (register_autograd over the *_backward ops), so
 autograd, FakeTensor and torch.compile see one op per native call.
 The implementations raise on non-CUDA or non-contiguous tensors as the reference's AT_ASSERTM does;
 there is no CPU path.
 """
+from typing import Optional
+
 import torch
 
 from ._lib import LIB, AttnBwdParams, AttnParams, MMT_BF16, MMT_F32, MMT_F64, check
@@ -238,6 +247,117 @@ def _mam_backward(ctx, dout, dlse):
 
 
 mam_attention_forward.register_autograd(_mam_backward, setup_context=_mam_setup)
+
+
+# --------------------------------------------------------------------------- candidate elimination
+@torch.library.custom_op("mmt::ce_select", mutates_args=())
+def ce_select(qkv: torch.Tensor, template_mask: Optional[torch.Tensor], gidx_in: Optional[torch.Tensor], n_t: int,
+              heads: int, keep: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """candidate_elimination's discrete part (asymmetric_shared_ce.py:52-102) on qkv [2B][n_t + n_s][3C]
+    (bf16: MFMA scores, or fp32), RGB sequences first: attn_mean [B][2 n_s] fp32 = the softmax over
+    [k_s_V | k_s_I] of the template queries [q_mt_V ; q_mt_I], averaged over the heads and over the
+    queries template_mask [B][2 n_t] (uint8 / bool, None = all) selects; order [2B][keep] int32 = each
+    modality's search tokens by attn_mean descending (ties by index), the first `keep`; gidx_out
+    [2B][keep] = gidx_in[order] (gidx_in [2B][n_s] int32, None = identity).  Not differentiable: only
+    the indices leave get_token_from_attn (:31-46), so there is no autograd formula."""
+    _need(qkv, "qkv", (torch.bfloat16, torch.float32))
+    S, rows, C3 = qkv.shape
+    C, Bm, n_s = C3 // 3, S // 2, rows - n_t
+    if S % 2 or n_s <= 0 or not 0 < keep <= n_s:
+        raise RuntimeError("ce_select: qkv (2B, n_t + n_s, 3C) with 0 < keep <= n_s expected")
+    dev = qkv.device
+    nq = 2 * n_t
+    count = None
+    if template_mask is not None:
+        _need(template_mask, "template_mask", (torch.uint8, torch.bool))
+        if tuple(template_mask.shape) != (Bm, nq):
+            raise RuntimeError("ce_select: template_mask (B, 2 n_t) expected")
+        template_mask = template_mask.view(torch.uint8) if template_mask.dtype == torch.bool else template_mask
+        count = template_mask.sum(1, keepdim=True, dtype=torch.float32)  # on the device: capturable
+    if gidx_in is not None:
+        _need(gidx_in, "gidx_in", (torch.int32,))
+        if tuple(gidx_in.shape) != (S, n_s):
+            raise RuntimeError("ce_select: gidx_in (2B, n_s) expected")
+    bf = qkv.dtype == torch.bfloat16
+    nparts = heads * (nq // (16 if bf else 8))
+    part = torch.empty(Bm * max(nparts, 1) * 2 * n_s, device=dev, dtype=torch.float32)
+    check(LIB.mmt_ce_t2s_attention_masked(qkv.data_ptr(), part.data_ptr(),
+                                          template_mask.data_ptr() if template_mask is not None else None, Bm, rows,
+                                          n_t, n_s, C, heads, (C // heads) ** -0.5, MMT_BF16 if bf else MMT_F32,
+                                          _stream()), "mmt_ce_t2s_attention_masked")
+    order = torch.empty(S, n_s, device=dev, dtype=torch.int32)
+    gidx = torch.empty(S, n_s, device=dev, dtype=torch.int32)
+    mean = torch.empty(Bm, 2 * n_s, device=dev, dtype=torch.float32)
+    # the sums over heads and queries times 1 / (heads * queries); with a mask the per-frame query count is
+    # divided out on the device (no host read: the op can be captured)
+    check(LIB.mmt_ce_select(part.data_ptr(), nparts, Bm, n_s, keep, n_s, gidx_in.data_ptr() if gidx_in is not None
+                            else None, gidx.data_ptr(), order.data_ptr(), mean.data_ptr(),
+                            1.0 / (heads * (nq if count is None else 1)), _stream()), "mmt_ce_select")
+    if count is not None:
+        mean = mean / count
+    return order[:, :keep].contiguous(), gidx[:, :keep].contiguous(), mean
+
+
+@ce_select.register_fake
+def _(qkv, template_mask, gidx_in, n_t, heads, keep):
+    S, rows, _ = qkv.shape
+    return (qkv.new_empty(S, keep, dtype=torch.int32), qkv.new_empty(S, keep, dtype=torch.int32),
+            qkv.new_empty(S // 2, 2 * (rows - n_t), dtype=torch.float32))
+
+
+@torch.library.custom_op("mmt::ce_index_invert", mutates_args=())
+def ce_index_invert(idx: torch.Tensor, n_out: int) -> torch.Tensor:
+    """idx [S][n_in] int32 -> [S][n_out] int32 with out[s][idx[s][j]] = j and -1 elsewhere (entries outside
+    [0, n_out) skipped): the index vector of a row gather's backward."""
+    _need(idx, "idx", (torch.int32,))
+    S, n_in = idx.shape
+    out = torch.empty(S, n_out, device=idx.device, dtype=torch.int32)
+    check(LIB.mmt_ce_index_invert(idx.data_ptr(), n_in, out.data_ptr(), n_out, S, _stream()), "mmt_ce_index_invert")
+    return out
+
+
+@ce_index_invert.register_fake
+def _(idx, n_out):
+    return idx.new_empty(idx.shape[0], n_out)
+
+
+@torch.library.custom_op("mmt::ce_rows_gather", mutates_args=())
+def ce_rows_gather(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """x [S][rows][C] fp32, idx [S][n] int32 -> y [S][n][C] with y[s][r] = x[s][idx[s][r]], a zero row where
+    idx is outside [0, rows): the pruning of the search tokens (idx = template rows, then the kept rows in
+    sorted order) and their recovery (idx = the inverted global index), _recover_search
+    asymmetric_shared_ce.py:426-447."""
+    _need(x, "x", (torch.float32,))
+    _need(idx, "idx", (torch.int32,))
+    S, rows, C = x.shape
+    if idx.dim() != 2 or idx.shape[0] != S:
+        raise RuntimeError("ce_rows_gather: idx (S, n) expected")
+    n = idx.shape[1]
+    y = torch.empty(S, n, C, device=x.device, dtype=torch.float32)
+    check(LIB.mmt_ce_rows_gather(x.data_ptr(), rows, y.data_ptr(), n, idx.data_ptr(), S, C, _stream()),
+          "mmt_ce_rows_gather")
+    return y
+
+
+@ce_rows_gather.register_fake
+def _(x, idx):
+    return x.new_empty(x.shape[0], idx.shape[1], x.shape[2])
+
+
+def _rows_setup(ctx, inputs, output):
+    x, idx = inputs
+    ctx.rows = x.shape[1]
+    ctx.save_for_backward(idx)
+
+
+def _rows_backward(ctx, dy):
+    # distinct indices: every source row feeds at most one destination row, so the scatter is a gather by
+    # the inverted index (zeros where a row was pruned), with no atomics
+    idx, = ctx.saved_tensors
+    return ce_rows_gather(dy.float().contiguous(), ce_index_invert(idx, ctx.rows)), None
+
+
+ce_rows_gather.register_autograd(_rows_backward, setup_context=_rows_setup)
 
 
 def mam_attention(qkv, n_t, heads):

@@ -1450,6 +1450,23 @@ class HipOps:
         return asym_attention_from_mam(HipOps.mam_attention, qkv, Bh, n_t, heads)
 
     @staticmethod
+    def ce_select(qkv, template_mask, gidx_in, n_t, heads, keep):
+        """(order, gidx_out, attn_mean) of one elimination stage (mmt::ce_select; no gradient)."""
+        from .ops import ce_select
+        return ce_select(qkv, template_mask, gidx_in, n_t, heads, keep)
+
+    @staticmethod
+    def ce_rows_gather(x, idx):
+        """Indexed copy of fp32 token rows, zero rows where idx < 0 (mmt::ce_rows_gather, with autograd)."""
+        from .ops import ce_rows_gather
+        return ce_rows_gather(x, idx)
+
+    @staticmethod
+    def ce_index_invert(idx, n_out):
+        from .ops import ce_index_invert
+        return ce_index_invert(idx, n_out)
+
+    @staticmethod
     def conv3x3(x, w, b, up=1, keep_pad=False, prep=None):
         """The corner head's 3x3 convolutions on NHWC maps (_HipConv3x3), operands cast to bf16 (autocast runs
         the nearest upsampling of the pyramid inputs in fp32); up: of the nearest upsampling of x (not
@@ -1702,11 +1719,99 @@ def _backbones_rgbt(net, template, online_template, search, ops, dpr, tokens=Fal
             backbone_forward(net.backbone_i, template[1], online_template[1], search[1], ops, dpr))
 
 
-def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_PATH_RATE):
+def _ce_attn_mean_torch(qkv, Bh, n_t, heads, mask):
+    """attn_t2s averaged over the (masked) template queries and the heads (asymmetric_shared_ce.py:198-202,
+    :81-92) in plain torch: the stand-in of ops.ce_select's scoring for ops without it.  qkv (2 Bh, n, 3C),
+    RGB first -> (Bh, 2 lens) fp32 [RGB | TIR]."""
+    S, n, C3 = qkv.shape
+    C = C3 // 3
+    q, k, _ = qkv.float().view(S, n, 3, heads, C // heads).permute(2, 0, 3, 1, 4).unbind(0)
+    qt = torch.cat([q[:Bh, :, :n_t], q[Bh:, :, :n_t]], 2)
+    ks = torch.cat([k[:Bh, :, n_t:], k[Bh:, :, n_t:]], 2)
+    a = ((qt @ ks.transpose(-2, -1)) * (C // heads) ** -0.5).softmax(dim=-1)
+    if mask is not None:
+        L = a.shape[-1]
+        a = a[mask.to(torch.bool).unsqueeze(1).unsqueeze(-1).expand(-1, heads, -1, L)].view(Bh, heads, -1, L)
+    return a.mean(dim=2).mean(dim=1)
+
+
+def _ce_rows_gather(ops, x, idx):
+    """y[s][r] = x[s][idx[s][r]], zero rows where idx < 0 (x (S, rows, C) fp32, idx (S, n) int32), differentiable
+    in x: ops.ce_rows_gather (HipOps: mmt::ce_rows_gather, whose backward is the same kernel on the inverted
+    index) or aten's gather."""
+    fn = getattr(ops, "ce_rows_gather", None)
+    if fn is not None:
+        return fn(x.contiguous(), idx.contiguous())
+    C = x.shape[-1]
+    y = x.gather(1, idx.clamp(min=0).long().unsqueeze(-1).expand(-1, -1, C))
+    return torch.where((idx >= 0).unsqueeze(-1), y, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def _ce_index_invert(ops, idx, n_out):
+    """out[s][idx[s][j]] = j, -1 elsewhere (int32): ops.ce_index_invert or aten's scatter_."""
+    fn = getattr(ops, "ce_index_invert", None)
+    if fn is not None:
+        return fn(idx.contiguous(), n_out)
+    S, n_in = idx.shape
+    out = torch.full((S, n_out), -1, dtype=torch.int32, device=idx.device)
+    return out.scatter_(1, idx.long(), torch.arange(n_in, dtype=torch.int32, device=idx.device).expand(S, -1))
+
+
+def _ce_stage(ops, qkv, gidx, Bh, n_t, heads, keep, N, mask, forced, trace):
+    """One elimination's discrete part on the block's qkv (2 Bh, n_t + lens, 3C): (order (2 Bh, keep) int32
+    rows of the current search tokens to keep, in sorted order; the new gidx (2 Bh, keep) int32 original
+    positions).  Nothing here is differentiable and nothing needs to be: get_token_from_attn
+    (asymmetric_shared_ce.py:31-46) hands on only the sorted indices (sorted_attn is unused), so the gradient
+    of the elimination flows through the row gather alone, and the scoring runs on detached values.
+    forced: ((Bh, keep), (Bh, keep)) original positions to keep instead of the sorted ones; trace: a list that
+    receives ((gidx_v, gidx_i), attn_mean)."""
+    with torch.no_grad():
+        qkv = qkv.detach()
+        S, n, _ = qkv.shape
+        lens = n - n_t
+        dev = qkv.device
+        am = None
+        sel = getattr(ops, "ce_select", None)
+        if sel is not None and (forced is None or trace is not None):
+            order, gnew, am = sel(qkv.contiguous(), mask, gidx, n_t, heads, keep)  # gidx None: identity
+        if gidx is None and (sel is None or forced is not None):
+            gidx = torch.arange(lens, dtype=torch.int32, device=dev).repeat(S, 1)
+        if sel is None and (forced is None or trace is not None):
+            am = _ce_attn_mean_torch(qkv, Bh, n_t, heads, mask)
+            # descending, ties by index (get_token_from_attn sorts; the stable order is the kernel's)
+            order = torch.cat([torch.sort(a, dim=1, descending=True, stable=True)[1][:, :keep]
+                               for a in (am[:, :lens], am[:, lens:])], 0).to(torch.int32)
+            gnew = gidx.gather(1, order.long())
+        if forced is not None:
+            f = torch.cat([torch.as_tensor(x, device=dev)[:, :keep] for x in forced], 0).long()
+            inv = _ce_index_invert(None, gidx, N)  # original position -> current row (test hook: aten)
+            order = inv.gather(1, f)
+            if not (order.is_cuda and torch.cuda.is_current_stream_capturing()) and bool((order < 0).any()):
+                raise ValueError("ce_forced keeps a token that an earlier stage pruned")
+            gnew = f.to(torch.int32)
+        if trace is not None:
+            trace.append(((gnew[:Bh].clone(), gnew[Bh:].clone()), am))
+    return order, gnew
+
+
+def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_PATH_RATE, ce=None,
+                             ce_template_mask=None, ce_keep_rate=None, ce_forced=None, ce_trace=None):
     """Shared-backbone forward with the modalities stacked on the batch ([rgb; tir], 2B):
     mixformer_shared.py:143-159, :253-282 (per-modality LayerNorms, shared weights, standard MAM) or,
     asym, asymmetric_shared.py:137-154, :236-266 (cross-modal MAM).  Returns the search features
-    (2B, C, gs, gs) and the first template's tokens (2B, gt*gt, C) (the score decoder's memory)."""
+    (2B, C, gs, gs) and the first template's tokens (2B, gt*gt, C) (the score decoder's memory).
+
+    ce = {block: keep ratio}: candidate elimination (asymmetric_shared_ce.py CE_Block_Shared.forward :247-282,
+    VisionTransformer.forward :372-424).  After the attention residual of an eliminating block -- its ratio
+    < 1 and ce_keep_rate None or < 1 (:250-253); a given ce_keep_rate replaces every ratio (:270) -- the
+    search tokens of both modalities are pruned to math.ceil(ratio * lens) (:77-79; nothing happens when that
+    equals lens) by the template queries' mean attention (ce_template_mask (B, 2 n_t): over the masked
+    queries), kept in sorted order after the template tokens.  The fp32 stream stays packed (2B, n_t + lens,
+    C) and shrinks at every stage; gidx (2B, lens) int32 carries the survivors' original positions, and after
+    the last block they go back there, pruned positions as zero rows (_recover_search :426-447).  Pruning,
+    recovery and their backwards are all one indexed row copy (ops.ce_rows_gather); the scores carry no
+    gradient (_ce_stage).  ce_forced / ce_trace: test hooks (per stage a pair of (B, keep) original positions
+    to keep / a list receiving each stage's ((gidx_v, gidx_i), attn_mean))."""
     B2 = t.shape[0]
     Bh = B2 // 2
     C = bb.pos_embed_s.shape[-1]
@@ -1720,6 +1825,13 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
     pos = torch.cat([bb.pos_embed_t, bb.pos_embed_t, bb.pos_embed_s], 1)
     x = x.view(B2, ntok, C) + pos
     depth = len(bb.blocks)
+    if ce and ce_keep_rate is not None and ce_keep_rate >= 1:
+        ce = None
+    if ce and not asym:
+        raise ValueError("candidate elimination is defined for the cross-modal (asym) backbone")
+    if ce and ce_template_mask is not None:
+        ce_template_mask = ce_template_mask.to(device=x.device, dtype=torch.uint8).contiguous()
+    gidx, stage, n = None, 0, ntok  # n: rows per sequence of the packed stream
 
     def ln2(x, a, b):  # norm*_v on the RGB half, norm*_i on the TIR half (and x passed through)
         return _layer_norm_pass(ops, x, a, b)
@@ -1727,11 +1839,26 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
     for li, blk in enumerate(bb.blocks):
         dp = drop_path_rate * li / max(depth - 1, 1)
         xn, xr = ln2(x, blk.norm1_v, blk.norm1_i)
-        qkv = ops.linear(xn.view(B2 * ntok, C), blk.attn.qkv.weight, blk.attn.qkv.bias).view(B2, ntok, 3 * C)
+        qkv = ops.linear(xn.view(B2 * n, C), blk.attn.qkv.weight, blk.attn.qkv.bias).view(B2, n, 3 * C)
         a = ops.mam_attention_asym(qkv, Bh, n_t, H) if asym else ops.mam_attention(qkv, n_t, H)
-        x = _branch_residual(ops, xr, a.reshape(B2 * ntok, C), blk.attn.proj, dp, bb.training)
+        x = _branch_residual(ops, xr, a.reshape(B2 * n, C), blk.attn.proj, dp, bb.training)
+        if ce and li in ce:
+            ratio = ce[li] if ce_keep_rate is None else ce_keep_rate
+            lens = n - n_t
+            keep = math.ceil(ratio * lens)
+            if ratio < 1 and keep != lens:
+                order, gidx = _ce_stage(ops, qkv, gidx, Bh, n_t, H, keep, gs * gs, ce_template_mask,
+                                        ce_forced[stage] if ce_forced is not None else None, ce_trace)
+                head = _const(("ce_head", B2, n_t), x.device,
+                              lambda: torch.arange(n_t, dtype=torch.int32).repeat(B2, 1))
+                x = _ce_rows_gather(ops, x, torch.cat([head, order.to(torch.int32) + n_t], 1))
+                n = n_t + keep
+            stage += 1
         xn, xr = ln2(x, blk.norm2_v, blk.norm2_i)
-        x = _mlp_residual(ops, xr, xn.view(B2 * ntok, C), blk.mlp, dp, bb.training)
+        x = _mlp_residual(ops, xr, xn.view(B2 * n, C), blk.mlp, dp, bb.training)
+    if gidx is not None:  # _recover_search: row n_t + gidx[j] of the full stream is row n_t + j, zeros elsewhere
+        head = _const(("ce_head", B2, n_t), x.device, lambda: torch.arange(n_t, dtype=torch.int32).repeat(B2, 1))
+        x = _ce_rows_gather(ops, x, _ce_index_invert(ops, torch.cat([head, gidx + n_t], 1), ntok))
     return x[:, n_t:].transpose(1, 2).reshape(B2, C, gs, gs), x[:, :gt * gt]
 
 
@@ -2064,16 +2191,21 @@ def forward_boxes(net, template, online_template, search, ops):
     return torch.stack([(x0 + x1) / 2, (y0 + y1) / 2, (x1 - x0), (y1 - y0)], -1).view(-1, 1, 4)
 
 
-def module_forward(net, template, online_template, search, ops, run_score_head=False, gt_bboxes=None):
+def module_forward(net, template, online_template, search, ops, run_score_head=False, gt_bboxes=None,
+                   ce_template_mask=None, ce_keep_rate=None):
     """The drop-in module's forward with autograd (net.train() under grad mode; what the reference's
     MixFormerRGBTActor calls, actors/mixformer_rgbt.py:82-98, possibly wrapped in DDP + SyncBN,
     train_script_mixformer.py:105-110): MixFormer_RGBT.forward (mixformer.py:366-395),
     mixformer_shared.py:400-424, asymmetric_shared.py:349-368 and asymmetric_shared_online.py:351-413
     (score head on the predicted boxes: gt_bboxes is accepted and ignored, as the reference's forward
-    drops it at asymmetric_shared_online.py:374).  Returns
+    drops it at asymmetric_shared_online.py:374), and asymmetric_shared_ce.py:557-587 (variant asym_ce:
+    candidate elimination at net.ce_loc / net.ce_keep_ratio with the actor's ce_template_mask / ce_keep_rate,
+    actors/mixformer_rgbt.py:67-90; net.ce_forced / net.ce_trace are test hooks).  Returns
     ({"pred_boxes": (B,1,4)[, "pred_scores": (B,)]}, (B,1,4))."""
     variant = net.variant
     dpr = getattr(net, "drop_path_rate", DROP_PATH_RATE)
+    if variant != "asym_ce" and (ce_template_mask is not None or ce_keep_rate is not None):
+        raise TypeError("ce_template_mask / ce_keep_rate: the %s variant has no candidate elimination" % variant)
     if variant == "rgbt":
         s_v, s_i = _backbones_rgbt(net, template, online_template, search, ops, dpr, tokens=_token_rows(ops))
         tok = None
@@ -2081,9 +2213,16 @@ def module_forward(net, template, online_template, search, ops, run_score_head=F
         feats, tok = backbone_forward_stacked(net.backbone, torch.cat(template, 0), torch.cat(online_template, 0),
                                               torch.cat(search, 0), ops, asym=variant != "shared", drop_path_rate=dpr)
         s_v, s_i = feats.chunk(2, 0)
+    elif variant == "asym_ce":
+        feats, tok = backbone_forward_stacked(net.backbone, torch.cat(template, 0), torch.cat(online_template, 0),
+                                              torch.cat(search, 0), ops, asym=True, drop_path_rate=dpr,
+                                              ce=dict(zip(net.ce_loc, net.ce_keep_ratio)),
+                                              ce_template_mask=ce_template_mask, ce_keep_rate=ce_keep_rate,
+                                              ce_forced=getattr(net, "ce_forced", None),
+                                              ce_trace=getattr(net, "ce_trace", None))
+        s_v, s_i = feats.chunk(2, 0)
     else:
-        raise NotImplementedError("training forward of %s (candidate elimination with autograd) is not built; "
-                                  "its inference forward runs under eval() / no_grad()" % variant)
+        raise NotImplementedError("training forward of the %s variant is not built" % variant)
     with torch.autocast(s_v.device.type, dtype=torch.bfloat16, enabled=s_v.device.type == "cuda"):
         fused = fusion_forward(net.fusion_vi, s_v, s_i, ops)
         xyxy = head_forward(net.box_head, fused, ops)
@@ -2141,15 +2280,19 @@ def box_loss(pred_cxcywh, gt_xywh, iou_weight=2.0, l1_weight=5.0):
 
 def param_groups(net, lr):
     """base_functions.py:362-400 (rgbt strategy): pos_embed frozen; backbone_i 0.1 lr, backbone_v
-    0.02 lr, box_head 0.02 lr, fusion 1.0 lr except sampling_offsets / reference_points 0.1 lr."""
+    0.02 lr, box_head 0.02 lr, fusion 1.0 lr except sampling_offsets / reference_points 0.1 lr.  The
+    shared-backbone variants (:413-470, rgbt shared strategy): the one backbone 0.02 lr, the rest alike."""
     named = list(net.named_parameters())
     for n, p in named:
         p.requires_grad = "pos_embed" not in n
     proj = ("reference_points", "sampling_offsets")
     sel = lambda f: [p for n, p in named if p.requires_grad and f(n)]  # noqa: E731
-    return [
-        {"params": sel(lambda n: "backbone_i" in n), "lr": 0.1 * lr},
-        {"params": sel(lambda n: "backbone_v" in n), "lr": 0.02 * lr},
+    if not hasattr(net, "backbone_v"):
+        bbs = [{"params": sel(lambda n: "backbone" in n), "lr": 0.02 * lr}]
+    else:
+        bbs = [{"params": sel(lambda n: "backbone_i" in n), "lr": 0.1 * lr},
+               {"params": sel(lambda n: "backbone_v" in n), "lr": 0.02 * lr}]
+    return bbs + [
         {"params": sel(lambda n: "box_head" in n), "lr": 0.02 * lr},
         {"params": sel(lambda n: "fusion_vi" in n and not any(k in n for k in proj))},
         {"params": sel(lambda n: "fusion_vi" in n and any(k in n for k in proj)), "lr": 0.1 * lr},
@@ -2274,7 +2417,12 @@ def graph_capture_mode(collectives):
 class TrainStep:
     """One optimisation step: forward, loss, backward, (data-parallel gradient all-reduce), clip, AdamW.
 
-    net: the two-stream model (mmt_amd.model.build_mixformer_vit_rgbt) on the device.
+    net: the two-stream model (mmt_amd.model.build_mixformer_vit_rgbt) or one of the stacked variants (shared,
+    asym, asym_online, asym_ce: their module_forward) on the device.  For asym_ce, ce_template_mask (B, 2 n_t)
+    bool (ce_center_mask builds the reference's CTR_POINT one) and ce_keep_rate are the actor's two arguments
+    (actors/mixformer_rgbt.py:67-90); both are attributes and may be changed between eager steps.  The kept
+    token counts are host integers, so a captured step holds for the keep rate of capture time: replay raises
+    once it changed (the warm-up schedule costs one re-capture whenever ceil(rate * lens) changes).
     ddp: False (one process), True (GradBucketAllReduce over the default process group: bucketed RCCL
     all-reduce launched from the backward's gradient hooks, capturable with the rest of the step), or
     "torch" (torch.nn.parallel.DistributedDataParallel around the step's module, the reference's wrap;
@@ -2282,9 +2430,12 @@ class TrainStep:
     (buckets rounded to bf16: half the bytes on the links, an explicit numerics deviation)."""
 
     def __init__(self, net, ops, lr=1e-4, weight_decay=1e-4, grad_clip=0.1, iou_weight=2.0, l1_weight=5.0,
-                 ddp=False, grad_compress="none"):
+                 ddp=False, grad_compress="none", ce_template_mask=None, ce_keep_rate=None):
         self.net = net
         self.ops = ops
+        if getattr(net, "variant", "rgbt") != "asym_ce" and (ce_template_mask is not None or ce_keep_rate is not None):
+            raise ValueError("ce_template_mask / ce_keep_rate: the net has no candidate elimination")
+        self.ce_template_mask, self.ce_keep_rate = ce_template_mask, ce_keep_rate
         self.grad_clip, self.iou_weight, self.l1_weight = grad_clip, iou_weight, l1_weight
         self._captured_hparams = None
         self.reducer = None
@@ -2333,7 +2484,10 @@ class TrainStep:
         self.opt.zero_grad(set_to_none=True)  # autograd then hands each fresh gradient over as .grad
         if self.reducer is not None:
             self.reducer.begin()
-        pred = self.model(t, o, s)
+        if getattr(self.net, "variant", "rgbt") == "asym_ce":
+            pred = self.model(t, o, s, self.ce_template_mask, self.ce_keep_rate)
+        else:
+            pred = self.model(t, o, s)
         loss_fn = getattr(self.ops, "box_loss", None) or box_loss  # HipOps: one launch each way
         loss, stats = loss_fn(pred, gt_xywh, self.iou_weight, self.l1_weight)
         loss.backward()
@@ -2388,18 +2542,22 @@ class TrainStep:
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.graph_stats = self(t, o, s, gt_xywh)
         self.static_inputs = (t, o, s, gt_xywh)
+        self._static_mask = self.ce_template_mask  # captured by address: replay copies a new mask into it
         self._captured_hparams = self._hparams()
         return self.graph_stats
 
     def _hparams(self):
         return ([(g.get("lr"), g.get("weight_decay"), tuple(g.get("betas", ())), g.get("eps")) for g in self.opt.param_groups]
-                + [("grad_clip", self.grad_clip), ("iou_weight", self.iou_weight), ("l1_weight", self.l1_weight)])
+                + [("grad_clip", self.grad_clip), ("iou_weight", self.iou_weight), ("l1_weight", self.l1_weight),
+                   ("ce_keep_rate", self.ce_keep_rate)])
 
-    def replay(self, t=None, o=None, s=None, gt_xywh=None):
-        """One captured step; given inputs are first copied into the static ones (device copies).  The
+    def replay(self, t=None, o=None, s=None, gt_xywh=None, ce_template_mask=None):
+        """One captured step; given inputs (and, for asym_ce, a given ce_template_mask with the captured one's
+        shape) are first copied into the static ones (device copies).  The
         captured AdamW launches carry the learning rates / weight decays of capture time as kernel arguments,
         so a changed optimizer hyper-parameter (an LR scheduler step) raises instead of replaying stale
-        values: capture() again after changing them."""
+        values: capture() again after changing them.  The same holds for ce_keep_rate (asym_ce), which fixes the
+        captured row counts."""
         if self._captured_hparams is None:
             raise RuntimeError("TrainStep.replay: call capture() first")
         if self._hparams() != self._captured_hparams:
@@ -2410,20 +2568,39 @@ class TrainStep:
             for dst, src in zip(st + so + ss, t + o + s):
                 dst.copy_(src)
             sg.copy_(gt_xywh)
+        if ce_template_mask is not None:
+            if self._static_mask is None:
+                raise RuntimeError("TrainStep.replay: the step was captured without a ce_template_mask")
+            self._static_mask.copy_(ce_template_mask)
         self.graph.replay()
         return self.graph_stats
 
 
 class _Wrapped(torch.nn.Module):
-    """nn.Module view of forward_boxes (DDP needs a module whose forward runs the graph)."""
+    """nn.Module view of forward_boxes, or for the stacked variants of module_forward's boxes (DDP needs a module
+    whose forward runs the graph)."""
 
     def __init__(self, net, ops):
         super().__init__()
         self.net = net
         self.ops = ops
 
-    def forward(self, t, o, s):
-        return forward_boxes(self.net, t, o, s, self.ops)
+    def forward(self, t, o, s, ce_template_mask=None, ce_keep_rate=None):
+        if getattr(self.net, "variant", "rgbt") == "rgbt":
+            return forward_boxes(self.net, t, o, s, self.ops)
+        return module_forward(self.net, t, o, s, self.ops, ce_template_mask=ce_template_mask,
+                              ce_keep_rate=ce_keep_rate)[1]
+
+
+def ce_center_mask(B, template_grid, device=None):
+    """The reference's CTR_POINT ce_template_mask (generate_mask_cond, lib/utils/ce_utils.py:14-38) for B frames
+    and a template grid of template_grid x template_grid tokens: (B, 4 template_grid^2) bool in the query order
+    [template_V, online_V, template_I, online_I], true at the centre token (g - 1) // 2 of each grid (the
+    reference's table: 3 of 8, 5 of 12, 3 of 7, 6 of 14)."""
+    g = int(template_grid)
+    m = torch.zeros(B, 4, g, g, dtype=torch.bool, device=device)
+    m[:, :, (g - 1) // 2, (g - 1) // 2] = True
+    return m.view(B, 4 * g * g)
 
 
 # ----------------------------------------------------------------------------- score-head training
