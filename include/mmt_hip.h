@@ -48,6 +48,8 @@
  *       tracker_utils.py:24-48 (cv2 crop/pad/resize, colour map, normalise)
  *   mmt_track_update            map_box_back + clip_box, lib/test/tracker/mixformer_vit_rgbt.py:92-95,
  *       :124-131, lib/utils/box_ops.py:155-164
+ *   mmt_sample_target_table / mmt_track_update_slots  the same two for N sequences per launch (the
+ *       batched tracker): crop descriptors in a device table, per-slot frame size and active mask
  */
 #ifndef MMT_HIP_H_
 #define MMT_HIP_H_
@@ -478,12 +480,38 @@ typedef struct {
 
 int mmt_sample_target(const mmt_crop_params* p, int n, void* stream);
 
+/* The same crops from a descriptor table in DEVICE memory: table_dev[n], any n >= 1, all of out_sz
+ * (the batched tracker: slots x modalities entries per step; design point 128).  A captured graph
+ * holds only table_dev, so the host re-points an entry (image, H, W, out, ...) with a small copy
+ * between replays, e.g. when a tracker slot takes the next sequence with another frame size.
+ * Everything an entry points to (image, box, lut, out, patch, crop) is device memory.
+ * enable_dev: NULL (all entries) or n bytes, entry i runs iff enable_dev[i] != 0.
+ * The host cannot check device-resident entries, so the kernel does: an entry is SKIPPED -- none
+ * of out / patch / crop is written -- when its enable byte is 0, image or box is NULL, out and
+ * patch are both NULL, H <= 0 or W <= 0, factor is not > 0, or its out_sz differs from the launch's
+ * out_sz.  (Pointers that are non-NULL but wrong cannot be detected: the owner of the table keeps
+ * every entry either valid or skippable.)  The arithmetic per entry is mmt_sample_target's, bit
+ * for bit.  MMT_EBADARG (before any launch): table_dev NULL, n <= 0, out_sz <= 0, or
+ * n * ceil(out_sz^2 / 256) blocks past the grid limit 2^31 - 1. */
+int mmt_sample_target_table(const mmt_crop_params* table_dev, const uint8_t* enable_dev, int n, int out_sz,
+                            void* stream);
+
 /* Box post-processing of the trackers (lib/test/tracker/mixformer_vit_rgbt.py:92-95, :124-131;
  * lib/utils/box_ops.py:155-164): for each of n trackers, pred = pred_cxcywh[i] * search_size /
  * resize_factor (fp32, as torch computes it), map_box_back against state[i] (fp64 x, y, w, h) and
  * crop[i][3] = resize_factor, clip_box(H, W, margin); the result replaces state[i]. */
 int mmt_track_update(const float* pred_cxcywh, const double* crop, double* state, int n, int H, int W,
                      int search_size, double margin, void* stream);
+
+/* The same for n tracker slots with a frame size each: hw[i] = (H, W) int32, the slot's crop record
+ * at crop + i * crop_stride doubles (crop_stride >= 4; the batched tracker keeps (N, 2, 4) records:
+ * 8), and active: NULL (all slots) or n bytes.  A slot with active[i] == 0 (or H <= 0 or W <= 0)
+ * keeps state[i] bitwise unchanged and its pred / crop are not read.  Per-slot arithmetic as
+ * mmt_track_update.  MMT_EBADARG: a NULL pred / crop / state / hw, n <= 0, search_size <= 0,
+ * crop_stride < 4. */
+int mmt_track_update_slots(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
+                           const int32_t* hw, const uint8_t* active, int n, int search_size, double margin,
+                           void* stream);
 
 /* ---------------------------------------------------------------- training-step helpers
  * bf16 transpose: out[b][c][r] = in[b][r][c] for a rows x cols matrix (leading dimensions ld_in /

@@ -11,6 +11,10 @@
 //                       (lib/test/tracker/mixformer_vit_rgbt.py:92-95, :124-131: scale the predicted
 //                       cxcywh back to image pixels, map_box_back, lib/utils/box_ops.py:155-164
 //                       clip_box with margin 10), updating the device-resident state in place.
+//   mmt_sample_target_table / mmt_track_update_slots
+//                       the same two for the batched tracker (N sequences per step): the crop
+//                       descriptors in a device table of any length, a frame size and an active
+//                       flag per slot.  Same device functions, same bits.
 //
 // cv2 is not part of this image, so the resize arithmetic restates OpenCV's 8-bit INTER_LINEAR
 // path (imgproc resize.cpp: float source coordinate (d+0.5)*scale-0.5, 11-bit fixed-point weights
@@ -65,13 +69,12 @@ MMT_DEV int src_px(const mmt_crop_params& p, const Geo& g, int r, int c, int ch)
     return p.image[((int64_t)iy * p.W + ix) * 3 + ch];
 }
 
-__global__ __launch_bounds__(256) void sample_target_kernel(const CropBatch cb) {
-    const mmt_crop_params& p = cb.c[blockIdx.y];
+// One output pixel (idx = dy * out_sz + dx) of crop p with geometry g: resize, optional colour map,
+// normalise.  Shared by the by-value launch (sample_target_kernel) and the device-table launch
+// (sample_target_table_kernel), so both compute the same bits.
+MMT_DEV void sample_pixel(const mmt_crop_params& p, const Geo& g, int idx) {
     const int os = p.out_sz;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= os * os) return;
     const int dy = idx / os, dx = idx - dy * os;
-    const Geo g = crop_geometry(p);
     if (idx == 0 && p.crop) {
         p.crop[0] = g.x1;
         p.crop[1] = g.y1;
@@ -125,16 +128,51 @@ __global__ __launch_bounds__(256) void sample_target_kernel(const CropBatch cb) 
     }
 }
 
-__global__ void track_update_kernel(const float* __restrict__ pred, const double* __restrict__ crop,
-                                    double* __restrict__ state, int n, int H, int W, int search_size, double margin) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double rf = crop[i * 4 + 3];
+__global__ __launch_bounds__(256) void sample_target_kernel(const CropBatch cb) {
+    const mmt_crop_params& p = cb.c[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.out_sz * p.out_sz) return;
+    sample_pixel(p, crop_geometry(p), idx);
+}
+
+// The descriptors live in device memory (the captured tracking step holds only the table pointer,
+// so the host re-points an entry at another frame with a small copy).  Block b works on entry
+// b / tiles, pixels [(b % tiles) * 256, +256).  Nothing in a device-resident entry can be checked
+// by the host, so every condition mmt_sample_target rejects on the host makes the block return
+// here, before any store.  The entry and its fp64 geometry are read / computed by one thread and
+// shared through LDS: same device function, same operands, same results as the per-pixel call.
+__global__ __launch_bounds__(256) void sample_target_table_kernel(const mmt_crop_params* __restrict__ table,
+                                                                  const uint8_t* __restrict__ enable, int tiles,
+                                                                  int out_sz) {
+    __shared__ mmt_crop_params sp;
+    __shared__ Geo sg;
+    __shared__ int live;
+    const int e = blockIdx.x / tiles, tile = blockIdx.x - e * tiles;
+    if (threadIdx.x == 0) {
+        // the entry is read whether enabled or not (it is in bounds): its load and the enable byte's are
+        // in flight together, one step less in the chain enable -> entry -> box -> geometry
+        sp = table[e];
+        const int on = enable ? enable[e] : 1;
+        const int ok = on && sp.image && sp.box && (sp.out || sp.patch) && sp.H > 0 && sp.W > 0 && sp.out_sz == out_sz &&
+                       sp.factor > 0.0;
+        if (ok) sg = crop_geometry(sp);
+        live = ok;
+    }
+    __syncthreads();
+    if (!live) return;
+    const int idx = tile * 256 + threadIdx.x;
+    if (idx >= out_sz * out_sz) return;
+    sample_pixel(sp, sg, idx);
+}
+
+// map_box_back + clip_box of one tracker: pred (cx, cy, w, h) normalised to the search crop, rf the
+// crop's resize factor, s the state (x, y, w, h) updated in place.
+MMT_DEV void track_update_one(const float* __restrict__ pred, double rf, double* __restrict__ s, int H, int W,
+                              int search_size, double margin) {
     const float inv = 1.0f / (float)rf;  // torch: fp32 tensor / python float = tensor * (1 / (float)scalar)
     double b[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) b[j] = (double)((pred[i * 4 + j] * (float)search_size) * inv);
-    double* s = state + i * 4;
+    for (int j = 0; j < 4; ++j) b[j] = (double)((pred[j] * (float)search_size) * inv);
     const double cx_prev = s[0] + 0.5 * s[2], cy_prev = s[1] + 0.5 * s[3];
     const double half = 0.5 * search_size / rf;
     const double cx = b[0] + (cx_prev - half), cy = b[1] + (cy_prev - half);
@@ -148,6 +186,26 @@ __global__ void track_update_kernel(const float* __restrict__ pred, const double
     s[1] = y1;
     s[2] = fmax(margin, x2 - x1);
     s[3] = fmax(margin, y2 - y1);
+}
+
+__global__ void track_update_kernel(const float* __restrict__ pred, const double* __restrict__ crop,
+                                    double* __restrict__ state, int n, int H, int W, int search_size, double margin) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    track_update_one(pred + i * 4, crop[i * 4 + 3], state + i * 4, H, W, search_size, margin);
+}
+
+// Per-slot frame size, a stride between the crop records, and a mask: an inactive slot (or one whose
+// frame size is not set) keeps its state untouched.
+__global__ void track_update_slots_kernel(const float* __restrict__ pred, const double* __restrict__ crop,
+                                          int crop_stride, double* __restrict__ state, const int32_t* __restrict__ hw,
+                                          const uint8_t* __restrict__ active, int n, int search_size, double margin) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (active && !active[i]) return;
+    const int H = hw[i * 2], W = hw[i * 2 + 1];
+    if (H <= 0 || W <= 0) return;
+    track_update_one(pred + i * 4, crop[(int64_t)i * crop_stride + 3], state + i * 4, H, W, search_size, margin);
 }
 
 }  // namespace
@@ -174,5 +232,24 @@ extern "C" int mmt_track_update(const float* pred_cxcywh, const double* crop, do
     if (!pred_cxcywh || !crop || !state || n <= 0 || H <= 0 || W <= 0 || search_size <= 0) return MMT_EBADARG;
     hipLaunchKernelGGL(track_update_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred_cxcywh, crop,
                        state, n, H, W, search_size, margin);
+    return launch_status();
+}
+
+extern "C" int mmt_sample_target_table(const mmt_crop_params* table_dev, const uint8_t* enable_dev, int n, int out_sz,
+                                       void* stream) {
+    if (!table_dev || n <= 0 || out_sz <= 0 || out_sz > 16384) return MMT_EBADARG;
+    const int64_t tiles = ((int64_t)out_sz * out_sz + 255) / 256;
+    if (tiles * n > 0x7fffffff) return MMT_EBADARG;  // one block per (entry, 256 pixels): the grid's x limit
+    hipLaunchKernelGGL(sample_target_table_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, (hipStream_t)stream,
+                       table_dev, enable_dev, (int)tiles, out_sz);
+    return launch_status();
+}
+
+extern "C" int mmt_track_update_slots(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
+                                      const int32_t* hw, const uint8_t* active, int n, int search_size, double margin,
+                                      void* stream) {
+    if (!pred_cxcywh || !crop || !state || !hw || n <= 0 || search_size <= 0 || crop_stride < 4) return MMT_EBADARG;
+    hipLaunchKernelGGL(track_update_slots_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred_cxcywh,
+                       crop, crop_stride, state, hw, active, n, search_size, margin);
     return launch_status();
 }

@@ -8,10 +8,13 @@ search_factor, search_size, checkpoint, save_all_boxes; `image` is [image_v, ima
 uint8 frames (numpy, or torch uint8 tensors already on the device); `track` returns
 {"target_bbox": [x, y, w, h]}.  The per-frame crop, preprocessing, forward and box
 post-processing run on the MI355X as one hipGraph (mmt_amd.tracking.RGBTTrackerCore).
+
+Each module also has `get_batch_tracker_class()`: the same tracker for `slots` sequences at once
+(mmt_amd.tracking.RGBTBatchTrackerCore: one hipGraph replay per frame of all sequences).
 """
 import torch
 
-from mmt_amd.tracking import RGBTTrackerCore
+from mmt_amd.tracking import RGBTBatchTrackerCore, RGBTTrackerCore
 
 try:  # the reference's BaseTracker (with its visdom helpers) when its lib/ is overlaid
     from lib.test.tracker.basetracker import BaseTracker
@@ -83,3 +86,44 @@ def make_tracker_class(builder, multimodal, online_score=False, kv_cache=KV_CACH
             return [cx_real - 0.5 * w, cy_real - 0.5 * h, w, h]
 
     return MixFormer
+
+
+def make_batch_tracker_class(builder, multimodal, online_score=False):
+    class BatchMixFormer:
+        """`slots` sequences on one network: initialize(slot, image, info) starts a sequence in a
+        slot, track(images) steps every active slot ({slot: [image_v, image_i]} in, {slot:
+        {"target_bbox": [x, y, w, h]}} out), release(slot) frees a slot for the next sequence.  A
+        slot that fails ("Too small bounding box.") is released and reported as {"error": exception}
+        in place of its box; the others go on.  mmt_amd.tracking.track_sequences drives `.core` over
+        a list of sequences.  save_all_boxes and the template K/V cache are not supported here."""
+
+        def __init__(self, params, dataset_name, slots):
+            if getattr(params, "save_all_boxes", False):
+                raise NotImplementedError("save_all_boxes is not supported by the batched tracker")
+            self.params = params
+            network = builder(params.cfg, train=False)
+            if getattr(params, "checkpoint", None):
+                ck = torch.load(params.checkpoint, map_location="cpu", weights_only=True)
+                network.load_state_dict(ck["net"], strict=True)
+            self.cfg = params.cfg
+            self.network = network.cuda()
+            self.network.eval()
+            self.update_intervals = _update_intervals(self.cfg, dataset_name)
+            self.slots = int(slots)
+            self.core = RGBTBatchTrackerCore(self.network, params.template_factor, params.template_size,
+                                             params.search_factor, params.search_size, self.update_intervals,
+                                             multimodal=multimodal, online_score=online_score,
+                                             kv_cache=getattr(params, "kv_cache", False), slots=self.slots)
+
+        def initialize(self, slot, image, info: dict):
+            """image: [image_v, image_i]; info["init_bbox"]: (bbox_v, bbox_i), the RGB box is used."""
+            self.core.assign(slot, image, info["init_bbox"][0])
+
+        def track(self, images, info: dict = None):
+            return {slot: ({"error": box} if isinstance(box, Exception) else {"target_bbox": box})
+                    for slot, box in self.core.track(images).items()}
+
+        def release(self, slot):
+            self.core.release(slot)
+
+    return BatchMixFormer

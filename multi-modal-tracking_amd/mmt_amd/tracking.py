@@ -236,3 +236,312 @@ class RGBTTrackerCore:
     def _check_crop(self, crop):
         if float(crop[:, 2].min()) < 1:
             raise Exception("Too small bounding box.")  # processing_utils.py:36-37
+
+
+# ---------------------------------------------------------------------- N sequences per replay
+def template_schedule(online_score, frame_id, update_intervals, pred_score=None, max_pred_score=-1.0):
+    """The per-frame template decisions of RGBTTrackerCore.track as a pure function of one slot's
+    counters: returns (crop, promotions, max_pred_score).
+
+    Plain trackers: crop = re-crop the online template at the new state (frame_id on an interval).
+    Online-score tracker: crop = the score gate (pred_score > 0.5 and > max_pred_score: the crop at
+    the new state becomes the candidate, online_max_template); promotions = how many intervals divide
+    frame_id: the first promotes the candidate to online template and resets the candidate to the
+    template, any further one (the reference's loop runs once per interval) then promotes that reset
+    candidate, i.e. the template itself.  max_pred_score is the value after the frame."""
+    due = 0
+    for i in update_intervals:
+        if frame_id % i == 0:
+            due += 1
+    if not online_score:
+        return due > 0, 0, max_pred_score
+    crop = pred_score > 0.5 and pred_score > max_pred_score
+    if crop:
+        max_pred_score = pred_score
+    if due:
+        max_pred_score = -1
+    return crop, due, max_pred_score
+
+
+class RGBTBatchTrackerCore:
+    """`slots` sequences tracked together: one tracking step of every slot is ONE hipGraph replay of
+      mmt_sample_target_table (2 * slots search crops, read from a crop-descriptor table in device memory)
+      -> the model's launch plan at batch `slots` -> mmt_track_update_slots (per-slot frame size, active mask)
+    and one host round trip for all slots.  A slot has its own frame size, state, frame counter and
+    template schedule (the decisions of RGBTTrackerCore.track, see template_schedule); when its
+    sequence ends, `assign` starts the next one in it.  The captured graph holds the table pointer,
+    not the frame pointers: a new frame size rewrites the slot's table entries and keeps the graph.
+
+    Arguments as RGBTTrackerCore, plus slots.  kv_cache is refused (NotImplementedError): slots update
+    their templates on different frames and the cache's template pass runs over the whole batch; a
+    per-slot template pass is a separate change.
+
+    Failures: a slot whose search crop side falls below 1 (the reference's "Too small bounding
+    box.") is released by `track`, and the returned mapping carries the Exception object in place of
+    that slot's box; the other slots are not affected."""
+
+    def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
+                 multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1):
+        if kv_cache:
+            raise NotImplementedError("the template K/V cache is per batch, the batched tracker's template "
+                                      "updates are per slot: kv_cache is not supported with slots")
+        if int(slots) < 1:
+            raise ValueError("slots must be >= 1")
+        self.net = network
+        self.slots = N = int(slots)
+        self.tf, self.ts, self.sf, self.ss = float(template_factor), int(template_size), float(search_factor), int(search_size)
+        self.update_intervals = list(update_intervals)
+        self.online_score = bool(online_score)
+        self.use_graph = bool(use_graph)
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self.dev
+        self.lut = torch.from_numpy(jet_lut().reshape(-1)).to(dev) if multimodal else None
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
+        self.state = z(N, 4, dt=torch.float64)
+        self.template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
+        self.online_template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
+        self.online_max_template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
+        self.search = [z(N, 3, self.ss, self.ss) for _ in range(2)]
+        self.search_crop = z(N, 2, 4, dt=torch.float64)
+        self.tmpl_crop = z(N, 2, 4, dt=torch.float64)
+        self.hw = z(N, 2, dt=torch.int32)
+        self.active = z(N, dt=torch.uint8)
+        self.frame_id = [0] * N
+        self.max_pred_score = [-1.0] * N
+        self.frames = [None] * N  # per slot [rgb, tir] flat uint8 buffers, at least H * W * 3 bytes
+        self._hw = [(0, 0)] * N
+        self._active = [False] * N
+        self._act = []  # the active slots, ascending
+        # crop tables: entry 2 b + m = slot b, modality m.  A zeroed entry (image NULL) is skipped by
+        # the kernel.  The template table writes where the tracker's schedule crops: the online
+        # template (plain trackers) or the candidate (online-score tracker).
+        self._esz = ctypes.sizeof(CropParams)
+        self._search_host, self._tmpl_host = (CropParams * (2 * N))(), (CropParams * (2 * N))()
+        self._search_tab, self._tmpl_tab = z(2 * N * self._esz, dt=torch.uint8), z(2 * N * self._esz, dt=torch.uint8)
+        self._search_enable, self._tmpl_enable = z(2 * N, dt=torch.uint8), z(2 * N, dt=torch.uint8)
+        self._tmpl_dst = self.online_max_template if self.online_score else self.online_template
+        self._fview = [None] * N  # per slot the (H, W, 3) views of its frame buffers
+        self._readback = [self.state.view(-1), self.search_crop[:, 0, 2]]  # what a step returns to the host
+        self._graph = self._plan = self._rt = self._ws = None
+        self.last_scores = None  # online-score tracker: every slot's sigmoid(score) of the last step
+
+    # ------------------------------------------------------------------ tables and frames
+    def _write_entries(self, b):
+        """Slot b's four descriptors, from its frame buffers and size, into the device tables."""
+        H, W = self._hw[b]
+        self._fview[b] = [buf[:H * W * 3].view(H, W, 3) for buf in self.frames[b]]
+        for m in range(2):
+            im = self._fview[b][m]
+            lut = self.lut if m == 1 else None
+            self._search_host[2 * b + m] = crop_params(im, self.state[b], self.sf, self.ss, out=self.search[m][b].view(-1),
+                                                       crop=self.search_crop[b, m], lut=lut)
+            self._tmpl_host[2 * b + m] = crop_params(im, self.state[b], self.tf, self.ts, out=self._tmpl_dst[m][b].view(-1),
+                                                     crop=self.tmpl_crop[b, m], lut=lut)
+        lo, hi = 2 * b * self._esz, (2 * b + 2) * self._esz
+        for host, tab in ((self._search_host, self._search_tab), (self._tmpl_host, self._tmpl_tab)):
+            tab[lo:hi].copy_(torch.frombuffer(host, dtype=torch.uint8)[lo:hi])
+        self.hw[b].copy_(torch.tensor([H, W], dtype=torch.int32))
+
+    def _load_frames(self, b, image):
+        """Copy slot b's two (H, W, 3) uint8 frames (numpy or torch) into its device buffers; a new
+        frame size grows the buffers if needed and rewrites the slot's table entries."""
+        if not isinstance(image, (list, tuple)) or len(image) != 2:
+            raise ValueError("image must be [image_v, image_i]")
+        ims = [torch.as_tensor(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x for x in image]
+        H, W = ims[0].shape[:2]
+        if any(tuple(x.shape) != (H, W, 3) or x.dtype != torch.uint8 for x in ims) or H <= 0 or W <= 0:
+            raise ValueError("frames must be two (H, W, 3) uint8 images of the same size")
+        if self.frames[b] is None or self.frames[b][0].numel() < H * W * 3:
+            self.frames[b] = [torch.empty(H * W * 3, device=self.dev, dtype=torch.uint8) for _ in range(2)]
+            self._hw[b] = (0, 0)
+        if self._hw[b] != (H, W):
+            self._hw[b] = (H, W)
+            self._write_entries(b)
+        for dst, src in zip(self._fview[b], ims):
+            dst.copy_(src, non_blocking=src.device.type == "cuda")
+
+    def _set_active(self, b, on):
+        self._active[b] = bool(on)
+        self._act = [i for i in range(self.slots) if self._active[i]]
+        self.active[b] = int(on)
+        self._search_enable[2 * b:2 * b + 2] = int(on)
+
+    def _crop_templates(self, slots):
+        """One table launch: both modalities' template crops of `slots`, each at its slot's state."""
+        en = torch.zeros(2 * self.slots, dtype=torch.uint8)
+        for b in slots:
+            en[2 * b:2 * b + 2] = 1
+        self._tmpl_enable.copy_(en)
+        check(LIB.mmt_sample_target_table(self._tmpl_tab.data_ptr(), self._tmpl_enable.data_ptr(), 2 * self.slots, self.ts,
+                                          torch.cuda.current_stream().cuda_stream), "mmt_sample_target_table")
+
+    # ------------------------------------------------------------------ per-frame plan
+    def _build_step(self):
+        rt = self.net._runtime(self.dev)
+        self._rt = rt  # the graph points into this runtime's weights and workspace (see RGBTTrackerCore)
+        N = self.slots
+        model_plan = rt.plan_for_inputs(self.template, self.online_template, self.search, run_score_head=self.online_score)
+        ws = self._ws = rt.workspace(N)
+        plan = [(LIB.mmt_sample_target_table, (self._search_tab.data_ptr(), self._search_enable.data_ptr(), 2 * N, self.ss),
+                 "track_sample_target_table", None)]
+        plan += model_plan
+        plan.append((LIB.mmt_track_update_slots, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), 8, self.state.data_ptr(),
+                                                  self.hw.data_ptr(), self.active.data_ptr(), N, self.ss, 10.0),
+                     "track_update_slots", None))
+        self._plan = plan
+        if self.use_graph:
+            saved = self.state.clone()  # capture_plan runs the plan once: keep this frame's states
+            self._graph = rt.capture_plan(plan)
+            self.state.copy_(saved)
+        else:
+            self._graph = None
+
+    def _step(self):
+        if self._plan is not None and self.net._runtime(self.dev) is not self._rt:
+            self._graph = self._plan = None  # weights reloaded: re-plan, re-capture
+        if self._plan is None or (self.use_graph and self._graph is None):
+            self._build_step()
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            self._rt.run_plan(self._plan)
+
+    # ------------------------------------------------------------------ tracker API
+    def active_slots(self):
+        return list(self._act)
+
+    def assign(self, slot, image, init_bbox):
+        """Start a sequence in `slot`: first frame pair and its box (x, y, w, h)."""
+        b = int(slot)
+        if not 0 <= b < self.slots:
+            raise IndexError("slot %d of %d" % (b, self.slots))
+        self._load_frames(b, image)
+        self.state[b].copy_(torch.tensor([float(v) for v in init_bbox], dtype=torch.float64))
+        self._crop_templates([b])
+        for m in range(2):
+            src = self._tmpl_dst[m][b]
+            for dst in (self.template, self.online_template, self.online_max_template):
+                if dst is not self._tmpl_dst:  # the candidate starts as the template (reference defect D6)
+                    dst[m][b].copy_(src)
+        self.frame_id[b] = 0
+        self.max_pred_score[b] = -1.0
+        self._set_active(b, True)
+        if float(self.tmpl_crop[b, :, 2].min()) < 1:
+            self.release(b)
+            raise Exception("Too small bounding box.")  # processing_utils.py:36-37
+
+    def release(self, slot):
+        """Stop tracking in `slot`: its crops and box update are skipped and its state stays as it is."""
+        self._set_active(int(slot), False)
+
+    def track(self, images):
+        """One frame of every active slot.  images: {slot: [image_v, image_i]}, exactly the active
+        slots.  Returns {slot: [x, y, w, h]}; a slot that failed (released here) maps to its Exception."""
+        act = self._act
+        ok = len(images) == len(act)
+        for b in act:
+            ok = ok and b in images
+        if not ok:
+            raise ValueError("track needs one frame pair per active slot %s, got %s" % (act, sorted(images)))
+        if not act:
+            return {}
+        for b in act:
+            self._load_frames(b, images[b])
+            self.frame_id[b] += 1
+        self._step()
+        N = self.slots
+        parts = self._readback
+        if self.online_score:
+            parts = parts + [torch.sigmoid(self._ws["SC"].view(-1)).double()]
+        vals = torch.cat(parts).tolist()  # the step's one host round trip, for all slots
+        out, crop, promote = {}, [], []
+        for b in act:
+            if vals[4 * N + b] < 1:
+                self.release(b)
+                out[b] = Exception("Too small bounding box.")  # processing_utils.py:36-37
+                continue
+            out[b] = vals[4 * b:4 * b + 4]
+            score = vals[5 * N + b] if self.online_score else None
+            c, p, self.max_pred_score[b] = template_schedule(self.online_score, self.frame_id[b], self.update_intervals,
+                                                             score, self.max_pred_score[b])
+            if c:
+                crop.append(b)
+            if p:
+                promote.append((b, p))
+        if self.online_score:
+            self.last_scores = vals[5 * N:]
+        if crop:
+            self._crop_templates(crop)
+        if promote:
+            idx = torch.tensor([b for b, _ in promote], device=self.dev)
+            twice = [b for b, p in promote if p > 1]
+            for m in range(2):
+                self.online_template[m][idx] = self.online_max_template[m][idx]
+                self.online_max_template[m][idx] = self.template[m][idx]
+                if twice:  # a second interval on the same frame promotes the reset candidate
+                    i2 = torch.tensor(twice, device=self.dev)
+                    self.online_template[m][i2] = self.template[m][i2]
+        return out
+
+
+class SequenceBoxes(list):
+    """The boxes of one sequence ([x, y, w, h] per frame, the first being init_bbox); `error` is the
+    exception that ended the sequence early, or None."""
+    error = None
+
+
+def track_sequences(core, sequences, slots=None):
+    """Track every sequence of `sequences` on `core` (an RGBTBatchTrackerCore, or anything with its
+    assign / release / track and a `slots` count), keeping the slots full: a slot whose sequence ends
+    is released and takes the next one.  sequences: iterable of (name, frames, init_bbox), frames an
+    iterable of [image_v, image_i]; the first frame carries init_bbox.  Returns {name: SequenceBoxes}:
+    one box per frame; a sequence that failed keeps the boxes up to the failure and the exception in
+    `.error` (its slot was released by `core.track`, or never taken when `assign` raised)."""
+    n = int(core.slots if slots is None else slots)
+    pending = iter(sequences)
+    running = {}  # slot -> (name, frame iterator)
+    results = {}
+
+    def fill(slot):
+        for name, frames, init_bbox in pending:
+            it = iter(frames)
+            boxes = results[name] = SequenceBoxes()
+            first = next(it, None)
+            if first is None:
+                continue
+            try:
+                core.assign(slot, first, init_bbox)
+            except Exception as e:  # this sequence cannot start; the slot stays free for the next
+                boxes.error = e
+                continue
+            boxes.append([float(v) for v in init_bbox])
+            running[slot] = (name, it)
+            return
+
+    for slot in range(n):
+        fill(slot)
+    while running:
+        images = {}
+        for slot in sorted(running):
+            name, it = running[slot]
+            frame = next(it, None)
+            while frame is None:  # sequence done: free the slot, start the next sequence in it
+                core.release(slot)
+                del running[slot]
+                fill(slot)
+                if slot not in running:
+                    break
+                frame = next(running[slot][1], None)
+            if frame is not None:
+                images[slot] = frame
+        if not images:
+            break
+        for slot, box in core.track(images).items():
+            name = running[slot][0]
+            if isinstance(box, Exception):  # core.track released the slot
+                results[name].error = box
+                del running[slot]
+                fill(slot)
+            else:
+                results[name].append(box)
+    return results
