@@ -50,6 +50,9 @@
  *       :124-131, lib/utils/box_ops.py:155-164
  *   mmt_sample_target_table / mmt_track_update_slots  the same two for N sequences per launch (the
  *       batched tracker): crop descriptors in a device table, per-slot frame size and active mask
+ *   mmt_slot_copy               no reference counterpart: moves the rows of listed tracker slots between a
+ *       compact staging layout and the N-slot layout (the batched tracker's per-slot template K/V cache:
+ *       template crops in, per-layer K / V columns out), slot lists and segments in device memory
  */
 #ifndef MMT_HIP_H_
 #define MMT_HIP_H_
@@ -512,6 +515,32 @@ int mmt_track_update(const float* pred_cxcywh, const double* crop, double* state
 int mmt_track_update_slots(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
                            const int32_t* hw, const uint8_t* active, int n, int search_size, double margin,
                            void* stream);
+
+/* Slot-indexed row copy (the batched tracker's per-slot template K/V cache).  A segment describes one
+ * strided 2-D block per slot on each side: slot s, row r occupies row_bytes bytes at
+ * base + s * slot_stride + r * row_pitch.  For every list entry j < n and every segment, the block of
+ * source slot src_slot_dev[j] is copied to destination slot dst_slot_dev[j]; a NULL list is the identity
+ * (entry j reads / writes slot j).  segs_dev and both lists are DEVICE memory and are read by the kernel
+ * only: nothing is allocated, synchronised or read on the host, so a captured graph can be replayed with
+ * another slot list.  An entry is SKIPPED -- nothing is read through it, nothing is written -- when either
+ * of its slot indices is negative or not below its side's slot count (the caller pads lists with -1).
+ * Duplicate destination slots in one list are the caller's error.  All addresses, strides, pitches and
+ * row_bytes are multiples of 16 (16-B loads and stores throughout); rows * row_bytes < 2^35 per segment
+ * (a segment past it, or with a NULL side, rows <= 0 or row_bytes < 16, is skipped by the kernel).
+ * max_seg_bytes: the largest rows * row_bytes of the table, which sizes the grid (with n and nseg; never
+ * the lists' contents); a smaller value only leaves fewer workgroups to loop over the larger segments.
+ * MMT_EBADARG (before any launch): segs_dev NULL, nseg <= 0, n <= 0, src_slots <= 0, dst_slots <= 0, both
+ * lists NULL with src_slots != dst_slots, nseg or n above 65535, max_seg_bytes < 16 or not a multiple of
+ * 16, a misaligned table or list. */
+typedef struct {
+    const void* src;                          /* slot 0's first byte on each side */
+    void* dst;
+    int64_t src_slot_stride, dst_slot_stride; /* bytes between consecutive slots */
+    int64_t src_row_pitch, dst_row_pitch;     /* bytes between consecutive rows of a slot */
+    int32_t rows, row_bytes;                  /* rows per slot; bytes copied per row (% 16 == 0) */
+} mmt_slot_copy_seg;
+int mmt_slot_copy(const mmt_slot_copy_seg* segs_dev, int nseg, const int32_t* src_slot_dev, int src_slots,
+                  const int32_t* dst_slot_dev, int dst_slots, int n, int64_t max_seg_bytes, void* stream);
 
 /* ---------------------------------------------------------------- training-step helpers
  * bf16 transpose: out[b][c][r] = in[b][r][c] for a rows x cols matrix (leading dimensions ld_in /

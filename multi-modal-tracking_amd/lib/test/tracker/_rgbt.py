@@ -95,7 +95,8 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
         {"target_bbox": [x, y, w, h]}} out), release(slot) frees a slot for the next sequence.  A
         slot that fails ("Too small bounding box.") is released and reported as {"error": exception}
         in place of its box; the others go on.  mmt_amd.tracking.track_sequences drives `.core` over
-        a list of sequences.  save_all_boxes and the template K/V cache are not supported here."""
+        a list of sequences.  params.slot_cache / params.refresh_slots: the per-slot template K/V cache
+        (off by default); save_all_boxes and the whole-batch kv_cache are not supported here."""
 
         def __init__(self, params, dataset_name, slots):
             if getattr(params, "save_all_boxes", False):
@@ -113,7 +114,9 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
             self.core = RGBTBatchTrackerCore(self.network, params.template_factor, params.template_size,
                                              params.search_factor, params.search_size, self.update_intervals,
                                              multimodal=multimodal, online_score=online_score,
-                                             kv_cache=getattr(params, "kv_cache", False), slots=self.slots)
+                                             kv_cache=getattr(params, "kv_cache", False), slots=self.slots,
+                                             slot_cache=getattr(params, "slot_cache", False),
+                                             refresh_slots=getattr(params, "refresh_slots", None))
 
         def initialize(self, slot, image, info: dict):
             """image: [image_v, image_i]; info["init_bbox"]: (bbox_v, bbox_i), the RGB box is used."""

@@ -68,6 +68,11 @@ class ConvWprep(ctypes.Structure):
                 ("pad_", i32)]
 
 
+class SlotCopySeg(ctypes.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("src_slot_stride", i64), ("dst_slot_stride", i64),
+                ("src_row_pitch", i64), ("dst_row_pitch", i64), ("rows", i32), ("row_bytes", i32)]
+
+
 WPREP_MAX = 24
 
 _PROTOS = {
@@ -137,6 +142,7 @@ _PROTOS = {
     "mmt_track_update": [vp, vp, vp, i32, i32, i32, i32, f64, vp],
     "mmt_sample_target_table": [vp, vp, i32, i32, vp],
     "mmt_track_update_slots": [vp, vp, i32, vp, vp, vp, i32, i32, f64, vp],
+    "mmt_slot_copy": [vp, i32, vp, i32, vp, i32, i32, i64, vp],
     "mmt_adamw_chunk_elems": [],
     "mmt_adamw_step": [vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f32, i32, vp],
 }

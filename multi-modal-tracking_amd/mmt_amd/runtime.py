@@ -26,7 +26,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import LIB, GemmParams, AttnParams, check, MMT_F32, MMT_BF16, MMT_F16
+from ._lib import LIB, GemmParams, AttnParams, SlotCopySeg, check, MMT_F32, MMT_BF16, MMT_F16
 
 VARIANTS = ("rgbt", "shared", "asym", "asym_online", "asym_ce", "rgb")  # rgb: RGB-only MixFormer (config 1)
 
@@ -295,9 +295,12 @@ class MixFormerRGBTRuntime:
             W["spm.mlp_n"] = n
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, B):
-        if B in self._ws:
-            return self._ws[B]
+    def workspace(self, B, key=None):
+        """The buffers and plans of batch B, built once.  key: a second, separate workspace of the same
+        batch size (the slot cache's staging pass must not share buffers with the batch's own)."""
+        key = B if key is None else key
+        if key in self._ws:
+            return self._ws[key]
         d = self.d
         dev, dt, f32, ht = self.device, self.dtype, torch.float32, self.hdtype
         S, R, C = d.nmod * B, d.nmod * B * d.ntok, d.C
@@ -338,7 +341,7 @@ class MixFormerRGBTRuntime:
             ws["plan_score"] = self._build_plan(ws, True)
             ws["plan_spm"] = []  # the score decoder alone, on ROIS as given (forward with gt_bboxes)
             self._plan_spm(ws["plan_spm"], ws)
-        self._ws[B] = ws
+        self._ws[key] = ws
         return ws
 
     # ------------------------------------------------------------------ plan construction
@@ -479,7 +482,7 @@ class MixFormerRGBTRuntime:
                        r_mode=1, r_p0=nr, c_f32=1, **cp, **pseg)
         # --- transformer blocks
         if self.ce and part is not None:
-            raise NotImplementedError("the template K/V cache is not defined for candidate elimination")
+            refuse_cache_with_ce(self.variant)
         stage = 0
         for i in range(d.depth):
             gm = B * nr  # rows per modality group (nr shrinks after each elimination stage)
@@ -807,15 +810,15 @@ class MixFormerRGBTRuntime:
         return ws["SC"].view(-1)
 
     # ------------------------------------------------------------------ template K/V cache
-    def cache_workspace(self, B):
-        """Workspace of batch B plus the template K/V cache (the RGB MixFormer's
+    def cache_workspace(self, B, key=None):
+        """Workspace of batch B (workspace's key) plus the template K/V cache (the RGB MixFormer's
         set_online / forward_test, mixformer_vit/mixformer.py:308-323, which the RGB-T models
         lack, reference defect D2): one qkv buffer per layer, whose template rows the template
         pass ("plan_t") fills once per template update and whose search rows each frame's pass
         ("plan_s"; "plan_s_score" with the score head) fills before the layer's attention reads
         all of them.  Template queries attend template keys only, so template + search passes
         reproduce the full forward (same kernels, same per-row arithmetic)."""
-        ws = self.workspace(B)
+        ws = self.workspace(B, key)
         if "plan_t" not in ws:
             d = self.d
             ws["QKVL"] = [torch.empty(d.nmod * B * d.ntok, 3 * d.C, device=self.device, dtype=self.dtype)
@@ -855,6 +858,111 @@ class MixFormerRGBTRuntime:
             dst.copy_(src, non_blocking=True)
         self.run_plan(ws["plan_s_score"] if score else ws["plan_s"])
         return ws["BOX"], (ws["SC"].view(-1) if score else None)
+
+    # ------------------------------------------------------------------ per-slot template K/V cache
+    def slot_cache_workspace(self, N, D, template=None, online_template=None):
+        """cache_workspace(N) whose template rows can be refreshed per slot (the batched tracker: slots
+        change templates on different frames, so the batch-N template pass does not fit).  A staging
+        template pass of capacity D -- its own workspace, distinct from workspace(D) even when D == N,
+        with its own per-layer qkv buffers and KV1 -- runs the "t" plan at batch D on the templates of
+        up to D listed slots, and mmt_slot_copy moves rows in and out by a slot list in device memory:
+          gather   the listed slots' template / online_template crops -> the staging inputs
+          "t" plan at batch D (+ the score head's KV1 for asym_online)
+          scatter  per layer and modality the n_t template rows' K and V columns ([C, 3C) of each 3C row;
+                   the search pass never reads a template row's Q), and the slot's KV1 rows, -> the
+                   N-slot cache of cache_workspace(N).
+        template / online_template: the N-slot [rgb, tir] fp32 tensors the gather reads (default: the
+        batch-N workspace's own input buffers).  Returns the refresh state `sc` for
+        refresh_template_slots; sc["ws"] is cache_workspace(N), sc["stage"] the staging workspace.
+        The N-slot cache rows are zeroed when first created: a slot never assigned reads zeros."""
+        N, D = int(N), int(D)
+        if N < 1 or not 1 <= D <= N:
+            raise ValueError("slot cache needs 1 <= refresh capacity D <= N slots, got D=%d N=%d" % (D, N))
+        fresh = "plan_t" not in self._ws.get(N, ())
+        ws = self.cache_workspace(N)  # raises NotImplementedError for candidate elimination
+        if fresh:
+            for q in ws["QKVL"]:
+                q.zero_()
+            if "KV1" in ws:
+                ws["KV1"].zero_()
+        template = ws["in_t"] if template is None else list(template)
+        online_template = ws["in_o"] if online_template is None else list(online_template)
+        d = self.d
+        for src, dst in zip(template + online_template, ws["in_t"] + ws["in_o"]):
+            if src.shape != dst.shape or src.dtype != torch.float32 or not src.is_contiguous() or src.device != dst.device:
+                raise ValueError("slot templates must be contiguous fp32 %s tensors on %s" % (tuple(dst.shape), dst.device))
+        key = (N, D) + tuple(t.data_ptr() for t in template + online_template)
+        cache = ws.setdefault("slot_cache", {})
+        if key in cache:
+            return cache[key]
+        st = self.cache_workspace(D, key=("slot_stage", N, D))
+        if "slot_init" not in st:
+            st["slot_init"] = True
+            for t in st["in_t"] + st["in_o"] + st["in_s"]:
+                t.zero_()
+            for q in st["QKVL"]:
+                q.zero_()
+        es = ws["QKVL"][0].element_size()
+        C, ntok = d.C, d.ntok
+        img = 3 * d.ht * d.ht * 4
+        gather = [(src, dst, img, img, img, img, 1, img)
+                  for srcs, dsts in ((template, st["in_t"]), (online_template, st["in_o"])) for src, dst in zip(srcs, dsts)]
+        row = 3 * C * es
+        scatter = [(_ptr(st["QKVL"][i], m * D * ntok * 3 * C + C), _ptr(ws["QKVL"][i], m * N * ntok * 3 * C + C),
+                    ntok * row, ntok * row, row, row, d.n_t, 2 * C * es)
+                   for i in range(d.depth) for m in range(d.nmod)]
+        if self.variant == "asym_online":
+            r1 = 2 * C * 4
+            scatter.append((st["KV1"], ws["KV1"], d.n_t * r1, d.n_t * r1, r1, r1, d.n_t, r1))
+        slots = torch.full((D,), -1, device=self.device, dtype=torch.int32)
+        sc = {"N": N, "D": D, "ws": ws, "stage": st, "slots": slots, "graph": None,
+              "keep": (template, online_template)}
+        gt, gmax = self._slot_table(gather)
+        stab, smax = self._slot_table(scatter)
+        sc["tables"] = (gt, stab)
+        plan = [(LIB.mmt_slot_copy, (_ptr(gt), len(gather), _ptr(slots), N, None, D, D, gmax), "slot_gather", gt)]
+        plan += st["plan_t"]
+        plan.append((LIB.mmt_slot_copy, (_ptr(stab), len(scatter), None, D, _ptr(slots), N, D, smax), "slot_scatter", stab))
+        sc["plan"] = plan
+        sc["scatter_bytes_per_slot"] = sum(s[6] * s[7] for s in scatter)
+        cache[key] = sc
+        return sc
+
+    def _slot_table(self, segs):
+        """mmt_slot_copy_seg table in device memory from (src, dst, src_slot_stride, dst_slot_stride,
+        src_row_pitch, dst_row_pitch, rows, row_bytes) tuples (src / dst: tensors or addresses);
+        returns (table tensor, the largest rows * row_bytes)."""
+        arr = (SlotCopySeg * len(segs))()
+        for a, (src, dst, sss, dss, srp, drp, rows, rb) in zip(arr, segs):
+            a.src = src if isinstance(src, int) else src.data_ptr()
+            a.dst = dst if isinstance(dst, int) else dst.data_ptr()
+            a.src_slot_stride, a.dst_slot_stride, a.src_row_pitch, a.dst_row_pitch = sss, dss, srp, drp
+            a.rows, a.row_bytes = rows, rb
+            if (a.src | a.dst | sss | dss | srp | drp | rb) & 15:
+                raise ValueError("mmt_slot_copy segments must be 16-byte aligned")
+        tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        return tab, max(s[6] * s[7] for s in segs)
+
+    def refresh_template_slots(self, sc, slots, use_graph=True):
+        """Template pass of the listed slots of slot_cache_workspace's state `sc`, in list order, from
+        the N-slot template buffers into the N-slot cache: ceil(len(slots) / D) replays of the refresh
+        plan (captured once per state), each on one chunk of the list written into the device slot list
+        on the current stream.  A slot listed twice in one chunk is the caller's error.  Returns the
+        number of replays."""
+        chunks = slot_chunks(slots, sc["D"])
+        for c in chunks:
+            if any(b >= sc["N"] or b < -1 for b in c):
+                raise IndexError("slot list %s of %d slots" % (c, sc["N"]))
+        for c in chunks:
+            sc["slots"].copy_(torch.tensor(c, dtype=torch.int32), non_blocking=False)
+            if use_graph:
+                if sc["graph"] is None:
+                    sc["graph"] = self.capture_plan(sc["plan"])  # capture_plan runs the plan once before recording it
+                else:
+                    sc["graph"].replay()
+            else:
+                self.run_plan(sc["plan"])
+        return len(chunks)
 
     def plan_for_inputs(self, template, online_template, search, run_score_head=False, part=None):
         """The plan of batch B with its patch staging reading the given device tensors directly
@@ -906,6 +1014,23 @@ class MixFormerRGBTRuntime:
             self.run_plan(plan)
         self._graphs[(B, score)] = g
         return g
+
+
+def refuse_cache_with_ce(variant):
+    """The template K/V cache (whole-batch or per slot) has no candidate-elimination form: the pruning reads
+    the template queries' attention over the search keys of the current frame."""
+    if variant == "asym_ce":
+        raise NotImplementedError("the template K/V cache is not defined for candidate elimination")
+
+
+def slot_chunks(slots, capacity):
+    """The slot lists of the refresh replays: `slots` in order, cut into lists of `capacity` entries, the
+    last one padded with -1 (an entry mmt_slot_copy skips)."""
+    slots = [int(b) for b in slots]
+    D = int(capacity)
+    if D < 1:
+        raise ValueError("capacity must be >= 1")
+    return [slots[i:i + D] + [-1] * (D - len(slots[i:i + D])) for i in range(0, len(slots), D)]
 
 
 def ctypes_byref(p):

@@ -272,23 +272,42 @@ class RGBTBatchTrackerCore:
     sequence ends, `assign` starts the next one in it.  The captured graph holds the table pointer,
     not the frame pointers: a new frame size rewrites the slot's table entries and keeps the graph.
 
-    Arguments as RGBTTrackerCore, plus slots.  kv_cache is refused (NotImplementedError): slots update
-    their templates on different frames and the cache's template pass runs over the whole batch; a
-    per-slot template pass is a separate change.
+    Arguments as RGBTTrackerCore, plus slots, slot_cache and refresh_slots.  kv_cache (the whole-batch
+    template pass) is refused (NotImplementedError): slots update their templates on different frames;
+    slot_cache is its per-slot form.
+
+    slot_cache=True: the template K/V cache per slot (runtime.slot_cache_workspace).  The step graph is
+    mmt_sample_target_table -> the search-only pass at batch `slots` -> mmt_track_update_slots, and a
+    slot whose templates changed is DIRTY: `assign` wrote them, the schedule re-cropped its online
+    template (plain trackers) or promoted its candidate (online-score tracker; a candidate crop alone
+    does not dirty it).  The dirty slots are refreshed at the start of the next `track`, before the step
+    graph, in ascending slot order: ceil(dirty / refresh_slots) replays of one refresh graph (template
+    crops gathered by a device slot list, the template pass at batch refresh_slots, K / V rows
+    scattered), none when no slot is dirty.  `release` clears the slot's mark; a weight reload marks
+    every active slot.  refresh_slots defaults to min(8, slots).  refresh_replays counts the replays.
+    Candidate-elimination networks raise the runtime's NotImplementedError at construction.
 
     Failures: a slot whose search crop side falls below 1 (the reference's "Too small bounding
     box.") is released by `track`, and the returned mapping carries the Exception object in place of
     that slot's box; the other slots are not affected."""
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
-                 multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1):
+                 multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1, slot_cache=False,
+                 refresh_slots=None):
         if kv_cache:
-            raise NotImplementedError("the template K/V cache is per batch, the batched tracker's template "
-                                      "updates are per slot: kv_cache is not supported with slots")
+            raise NotImplementedError("kv_cache is the whole-batch template pass, the batched tracker's template "
+                                      "updates are per slot: use slot_cache=True (the per-slot template K/V cache)")
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         self.net = network
         self.slots = N = int(slots)
+        self.slot_cache = bool(slot_cache)
+        self.refresh_slots = min(8, N) if refresh_slots is None else int(refresh_slots)
+        if self.slot_cache and not 1 <= self.refresh_slots <= N:
+            raise ValueError("refresh_slots must be in 1..slots")
+        self._dirty = set()
+        self._sc = None
+        self.refresh_replays = 0
         self.tf, self.ts, self.sf, self.ss = float(template_factor), int(template_size), float(search_factor), int(search_size)
         self.update_intervals = list(update_intervals)
         self.online_score = bool(online_score)
@@ -324,6 +343,9 @@ class RGBTBatchTrackerCore:
         self._readback = [self.state.view(-1), self.search_crop[:, 0, 2]]  # what a step returns to the host
         self._graph = self._plan = self._rt = self._ws = None
         self.last_scores = None  # online-score tracker: every slot's sigmoid(score) of the last step
+        if self.slot_cache:  # the runtime's refusal, here rather than at the first track
+            from .runtime import refuse_cache_with_ce
+            refuse_cache_with_ce(getattr(network, "variant", None))
 
     # ------------------------------------------------------------------ tables and frames
     def _write_entries(self, b):
@@ -376,11 +398,20 @@ class RGBTBatchTrackerCore:
                                           torch.cuda.current_stream().cuda_stream), "mmt_sample_target_table")
 
     # ------------------------------------------------------------------ per-frame plan
+    def _slot_state(self, rt):
+        """The runtime's refresh state over this tracker's template buffers (built once per runtime)."""
+        return rt.slot_cache_workspace(self.slots, self.refresh_slots, self.template, self.online_template)
+
     def _build_step(self):
         rt = self.net._runtime(self.dev)
         self._rt = rt  # the graph points into this runtime's weights and workspace (see RGBTTrackerCore)
         N = self.slots
-        model_plan = rt.plan_for_inputs(self.template, self.online_template, self.search, run_score_head=self.online_score)
+        if self.slot_cache:
+            self._sc = self._slot_state(rt)
+            model_plan = rt.plan_for_inputs(None, None, self.search, run_score_head=self.online_score, part="s")
+        else:
+            model_plan = rt.plan_for_inputs(self.template, self.online_template, self.search,
+                                            run_score_head=self.online_score)
         ws = self._ws = rt.workspace(N)
         plan = [(LIB.mmt_sample_target_table, (self._search_tab.data_ptr(), self._search_enable.data_ptr(), 2 * N, self.ss),
                  "track_sample_target_table", None)]
@@ -399,8 +430,13 @@ class RGBTBatchTrackerCore:
     def _step(self):
         if self._plan is not None and self.net._runtime(self.dev) is not self._rt:
             self._graph = self._plan = None  # weights reloaded: re-plan, re-capture
+            if self.slot_cache:  # the new runtime's cache holds none of the templates
+                self._dirty.update(self._act)
         if self._plan is None or (self.use_graph and self._graph is None):
             self._build_step()
+        if self._dirty:  # slot cache: template pass of the slots whose templates changed
+            self.refresh_replays += self._rt.refresh_template_slots(self._sc, sorted(self._dirty), self.use_graph)
+            self._dirty.clear()
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -426,6 +462,8 @@ class RGBTBatchTrackerCore:
         self.frame_id[b] = 0
         self.max_pred_score[b] = -1.0
         self._set_active(b, True)
+        if self.slot_cache:
+            self._dirty.add(b)
         if float(self.tmpl_crop[b, :, 2].min()) < 1:
             self.release(b)
             raise Exception("Too small bounding box.")  # processing_utils.py:36-37
@@ -433,6 +471,7 @@ class RGBTBatchTrackerCore:
     def release(self, slot):
         """Stop tracking in `slot`: its crops and box update are skipped and its state stays as it is."""
         self._set_active(int(slot), False)
+        self._dirty.discard(int(slot))
 
     def track(self, images):
         """One frame of every active slot.  images: {slot: [image_v, image_i]}, exactly the active
@@ -472,6 +511,8 @@ class RGBTBatchTrackerCore:
             self.last_scores = vals[5 * N:]
         if crop:
             self._crop_templates(crop)
+        if self.slot_cache:  # the online template changed: re-crop (plain) or promotion (online score)
+            self._dirty.update([b for b, _ in promote] if self.online_score else crop)
         if promote:
             idx = torch.tensor([b for b, _ in promote], device=self.dev)
             twice = [b for b, p in promote if p > 1]

@@ -10,11 +10,21 @@ the initial boxes before every step (as bench.py's tracker_step does: synthetic 
 wanders).  The two sides alternate; each timing runs at least --seconds; --repeats gives the spread.
 
     python tools/batch_tracker_time.py --out profiles/batch_tracker_time.jsonl
-    rocprofv3 --kernel-trace --stats -d <dir> -o bt -- python tools/batch_tracker_time.py --trace-run 64
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bt -- python tools/batch_tracker_time.py --trace-run 64
     python tools/batch_tracker_time.py --kernel-stats <dir>/.../bt_kernel_stats.csv --slots 64
 
 --trace-run N: only a few steps of side (b) at N slots, for the kernel trace; --kernel-stats CSV: the
-crop-table and slot-update kernels' device time from that trace's stats file, appended to --out."""
+crop-table, slot-update and slot-copy kernels' device time from that trace's stats file, appended to --out.
+
+--slot-cache: instead of (a) against (b), the batched tracker without (b) and with (c) the per-slot template
+K/V cache (RGBTBatchTrackerCore(slot_cache=True, refresh_slots=--refresh-slots)), alternating in the same run
+on the same frames; also the refresh replays per 1000 steps at the tool's update interval, the refresh graph's
+time per replay, and the scatter launch of mmt_slot_copy alone between two device events with its achieved
+bytes/s, read + written.  With --trace-run the cached side is traced, and --kernel-stats then also splits
+mmt_slot_copy's launches by grid from the per-dispatch trace beside the stats file (the stats file sums the gather
+and the scatter under one kernel name) and gives the scatter's bytes/s inside the refresh plan.
+
+    python tools/batch_tracker_time.py --slot-cache --out profiles/batch_tracker_time.jsonl"""
 import argparse
 import csv
 import json
@@ -24,7 +34,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, W = 480, 640
-KERNELS = ("sample_target_table_kernel", "track_update_slots_kernel")
+KERNELS = ("sample_target_table_kernel", "track_update_slots_kernel", "slot_copy_kernel")
+INTERVAL = 200
 
 
 def kernel_stats(path, slots, variant):
@@ -35,6 +46,24 @@ def kernel_stats(path, slots, variant):
             if k in name:
                 rec[k] = {"calls": int(row["Calls"]), "avg_us": round(float(row["AverageNs"]) / 1e3, 2),
                           "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
+    # the stats file sums mmt_slot_copy's gather and scatter launches under one name: split them by grid in the
+    # per-dispatch trace beside it (the scatter is the launch with the most segments, grid y)
+    trace = path.replace("_kernel_stats.csv", "_kernel_trace.csv")
+    if trace != path and os.path.exists(trace):
+        by_grid = {}
+        for row in csv.DictReader(open(trace)):
+            if "slot_copy_kernel" in (row.get("Kernel_Name") or ""):
+                grid = tuple(int(row["Grid_Size_" + a]) // max(1, int(row["Workgroup_Size_" + a])) for a in "XYZ")
+                by_grid.setdefault(grid, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+        rec["slot_copy_by_grid"] = {"x".join(map(str, g)): {"calls": len(t), "avg_us": round(sum(t) / len(t), 2),
+                                                              "min_us": round(min(t), 2), "max_us": round(max(t), 2)}
+                                    for g, t in sorted(by_grid.items())}
+        if by_grid:
+            g = max(by_grid, key=lambda k: k[1])  # ViT-B bf16: 24 segments of 128 rows x 3072 B per listed slot
+            moved = 2 * g[2] * g[1] * 128 * 3072
+            t = by_grid[g]
+            rec["slot_copy_scatter"] = {"grid": list(g), "bytes_moved": moved, "avg_TBps": round(moved / (sum(t) / len(t)) / 1e6, 3),
+                                        "best_TBps": round(moved / min(t) / 1e6, 3), "copy_ceiling_TBps": 6.3}
     return rec
 
 
@@ -47,6 +76,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--trace-run", type=int, default=0)
     ap.add_argument("--kernel-stats", default="")
+    ap.add_argument("--slot-cache", action="store_true")
+    ap.add_argument("--refresh-slots", type=int, default=0, help="refresh capacity (0: the core's default)")
     args = ap.parse_args()
     out = open(args.out, "a")
 
@@ -83,11 +114,11 @@ def main():
 
     def sides(net, variant, N):
         mm = builders[variant][1]
-        singles = [RGBTTrackerCore(net, 2.0, 128, 5.0, 320, [200], multimodal=mm) for _ in range(N)]
+        singles = [RGBTTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], multimodal=mm) for _ in range(N)]
         for b, c in enumerate(singles):
             c.initialize(frames[0], init_box(b))
         inits = [c.state.clone() for c in singles]
-        batch = RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [200], multimodal=mm, slots=N)
+        batch = RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], multimodal=mm, slots=N)
         for b in range(N):
             batch.assign(b, frames[0], init_box(b))
         binit = batch.state.clone()
@@ -104,6 +135,54 @@ def main():
 
         return step_a, step_b, batch
 
+    def cache_sides(net, variant, N):
+        """(b) the uncached batched tracker, (c) the same with the per-slot template K/V cache."""
+        mm = builders[variant][1]
+        cores = []
+        for cached in (False, True):
+            c = RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], multimodal=mm, slots=N, slot_cache=cached,
+                                     refresh_slots=(args.refresh_slots or None) if cached else None)
+            for b in range(N):
+                c.assign(b, frames[0], init_box(b))
+            cores.append(c)
+        binit = cores[0].state.clone()
+
+        def stepper(c):
+            def step(i):
+                c.state.copy_(binit)
+                r = c.track({b: frames[(i + b) % 4] for b in range(N)})
+                assert len(r) == N and not any(isinstance(v, Exception) for v in r.values())
+            return step
+        return stepper(cores[0]), stepper(cores[1]), cores[0], cores[1]
+
+    def refresh_times(core, N):
+        """Host time per refresh replay (graph, synchronised) and device time of its scatter launch alone."""
+        rt, sc = core._rt, core._sc
+        D = sc["D"]
+        slots = list(range(D))
+        rt.refresh_template_slots(sc, slots)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(20):
+            rt.refresh_template_slots(sc, slots)
+        torch.cuda.synchronize()
+        per_replay = (time.perf_counter() - t0) / 20
+        fn, a, name, _ = sc["plan"][-1]
+        assert name == "slot_scatter"
+        st = torch.cuda.current_stream().cuda_stream
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for _ in range(3):
+            fn(*a, st)
+        ev[0].record()
+        for _ in range(50):
+            fn(*a, st)
+        ev[1].record()
+        torch.cuda.synchronize()
+        us = ev[0].elapsed_time(ev[1]) * 1e3 / 50
+        moved = 2 * D * sc["scatter_bytes_per_slot"]  # read + written, all D entries valid
+        return {"refresh_slots": D, "refresh_replay_us": round(per_replay * 1e6, 1), "scatter_launch_us": round(us, 2),
+                "scatter_bytes_moved": moved, "scatter_TBps": round(moved / us / 1e6, 3), "copy_ceiling_TBps": 6.3}
+
     def timed(step, steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -113,8 +192,44 @@ def main():
 
     if args.trace_run:
         variant = args.variants.split(",")[0]
+        if args.slot_cache:
+            _, step_c, _, core = cache_sides(network(variant), variant, args.trace_run)
+            timed(step_c, 30)
+            for _ in range(5):
+                core._rt.refresh_template_slots(core._sc, list(range(core._sc["D"])))
+            torch.cuda.synchronize()
+            return
         _, step_b, _ = sides(network(variant), variant, args.trace_run)
         timed(step_b, 30)
+        return
+
+    if args.slot_cache:
+        for variant in args.variants.split(","):
+            net = network(variant)
+            for N in [int(x) for x in args.slots.split(",")]:
+                step_b, step_c, plain, cached = cache_sides(net, variant, N)
+                n = {}
+                for name, step in (("b", step_b), ("c", step_c)):
+                    timed(step, 3)
+                    n[name] = max(5, int(args.seconds / (timed(step, 5) / 5)) + 1)
+                rates = {"b": [], "c": []}
+                r0, f0 = cached.refresh_replays, cached.frame_id[0]
+                for _ in range(args.repeats):
+                    for name, step in (("b", step_b), ("c", step_c)):
+                        rates[name].append(N * n[name] / timed(step, n[name]))
+                steps_c = cached.frame_id[0] - f0
+                rec = {"what": "tracker_step_slot_cache", "variant": variant, "slots": N, "dtype": "bf16", "frame": [H, W],
+                       "steps": n, "update_interval": INTERVAL, "hip_graph": cached._graph is not None,
+                       "unit": "sequence-frames/s",
+                       "refresh_replays_per_1000_steps": round(1000.0 * (cached.refresh_replays - r0) / steps_c, 2)}
+                for name, key in (("b", "batched_core"), ("c", "batched_core_slot_cache")):
+                    r = sorted(rates[name])
+                    rec[key] = {"median": round(r[len(r) // 2], 1), "min": round(r[0], 1), "max": round(r[-1], 1)}
+                rec["speedup_median"] = round(rec["batched_core_slot_cache"]["median"] / rec["batched_core"]["median"], 3)
+                rec.update(refresh_times(cached, N))
+                emit(rec)
+                del step_b, step_c, plain, cached
+                torch.cuda.empty_cache()
         return
 
     for variant in args.variants.split(","):
