@@ -15,9 +15,12 @@
 //   impl 17 / 21 / 22  bf16 range-checked exponent kernels (no reference point, exact fallback):
 //            32 (17 / 21) or 64 (22, the batched default) queries per wave; 21 = 17 with the two key
 //            blocks of a tile software-pipelined
-//   impl 23  (A/B build only, MMT_ATTN_AB) the 64-queries-per-wave kernel as a two-stage pipeline
-//            over (key block, query block) units with a sched_group_barrier issue pattern and
-//            256-query workgroups: bit-identical to 22, measured 6-10 % slower
+//   impl 29  attention_ps.hip: impl 22's math as a persistent kernel, one wave per SIMD
+//   impl 23-28  removed.  They were A/B-only experiments on impl 22 (23 / 26 / 27: a two-stage pipeline
+//            over (key block, query block) units with a sched_group_barrier issue pattern; 24 / 25: one
+//            wave per SIMD; 28: ping-pong), each bit-identical to 22 and measured slower.  DESIGN.md §8
+//            and profiles/ keep the numbers, git history keeps the code; the dispatcher rejects them.
+// Which keys a query block sees, and where they live, is stated once: MamBlock in attn_common.hpp.
 // Scores are computed transposed (S^T = K Q^T) so that each lane owns one query column: the softmax
 // statistics need no cross-lane reduction and the exponentiated scores are already laid out as the B
 // operand of O^T = V^T P^T (no LDS round trip for P).  V^T fragments come from ds_read_b64_tr_b16 on
@@ -32,29 +35,6 @@
 
 
 namespace {
-
-
-// XCD-aware bijective block remap (as gemm.hip): workgroups are dealt round-robin over the 8 XCDs,
-// so consecutive (query block, head, sequence) ids would put the query blocks of one (sequence,
-// head) on different XCDs, each fetching the same K / V rows into its own L2.  Giving each XCD a
-// contiguous run of ids (query block fastest) keeps those re-reads in one L2.  Speed only; applied
-// to grids larger than the chip (batched inference: B = 8 / 32 throughput kernel 33 -> 29 / 90 ->
-// 84 us), not to the single-wave batch-1 grid.
-MMT_DEV void attn_block_ids(int& bx, int& by, int& bz) {
-    const int nbx = gridDim.x, nby = gridDim.y, nwg = nbx * nby * gridDim.z;
-    if (nwg <= 256) {
-        bx = blockIdx.x;
-        by = blockIdx.y;
-        bz = blockIdx.z;
-        return;
-    }
-    const int orig = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
-    const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-    bx = lin % nbx;
-    by = (lin / nbx) % nby;
-    bz = lin / (nbx * nby);
-}
 
 
 template <typename T>
@@ -74,20 +54,11 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
     __shared__ u32x4 kl[2][KB * KCH];
     __shared__ __attribute__((aligned(16))) char vl[2][KB * VROW];
 
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;  // rows between sequences
-    const int nqb_t = (n_t + 63) / 64;
     int bx, h, s;
-    attn_block_ids(bx, h, s);
-    const int qb = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qb < nqb_t;
-    const int q0 = tmpl ? qb * 64 : n_t + (qb - nqb_t) * 64;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const T* qkv = (const T*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
+    attn_block_ids<false>(bx, h, s);
+    const MamBlock<T, 64> blk(p, bx, s);
+    const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
+    const int64_t pitch = blk.pitch;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int l16 = lane & 15, lg = lane >> 4;
@@ -97,7 +68,7 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const int q = q0 + 16 * QT * w + 16 * qt + l16;
-        const T* qp = qkv + ((int64_t)s * pitch + min(q, qend - 1)) * rs + h * D;  // clamped, never stored
+        const T* qp = blk.q_row(q) + h * D;
 #pragma unroll
         for (int t = 0; t < QCH; ++t) qf[qt][t] = *(const u32x4*)(qp + (4 * t + lg) * (16 / (int)sizeof(T)));
     }
@@ -105,15 +76,6 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
     // ---- K/V staging
     constexpr int PER = KB * KCH / NTH;  // chunks per thread per tile (4 / 8)
     const int ch = tid % KCH;
-    auto key_ptr = [&](int kk) -> const T* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs + h * D;
-    };
     // K/V loads are unconditional (rows past Lk re-read key Lk-1 and are masked in the scores;
     // their V rows are multiplied by p = 0): a guarded load would make hipcc drain vmcnt(0).
     u32x4 rk[PER], rv[PER];
@@ -122,7 +84,7 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
         for (int i = 0; i < PER; ++i) {
             const int row = (tid + NTH * i) / KCH;
             const int kk = min(kt * KB + row, Lk - 1);
-            const T* kp = key_ptr(kk) + ch * (16 / (int)sizeof(T));
+            const T* kp = blk.key_row(kk) + h * D + ch * (16 / (int)sizeof(T));
             rk[i] = *(const u32x4*)(kp + C);
             rv[i] = *(const u32x4*)(kp + 2 * C);
         }
@@ -147,7 +109,7 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
         for (int dt = 0; dt < 4; ++dt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-    const int nkt = (Lk + KB - 1) / KB;
+    const int nkt = blk.nkt();
     load_kv(0);
     store_kv(0);
     lds_barrier();
@@ -333,21 +295,12 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
     MMT_ASTAMP(0, "s_memrealtime");
     MMT_ASTAMP(1, "s_memtime");
 
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;  // rows between sequences
-    const int nqb_t = (n_t + 63) / 64;
     int bx, h, s;
-    attn_block_ids(bx, h, s);  // (grouping a (sequence, head)'s query blocks on one XCD measured
-                               // slower at batch 1: 8.94 vs 8.47 us in the frame)
-    const int qb = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qb < nqb_t;
-    const int q0 = tmpl ? qb * 64 : n_t + (qb - nqb_t) * 64;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const T* qkv = (const T*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
+    attn_block_ids<false>(bx, h, s);  // (grouping a (sequence, head)'s query blocks on one XCD measured
+                                      // slower at batch 1: 8.94 vs 8.47 us in the frame)
+    const MamBlock<T, 64> blk(p, bx, s);
+    const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
+    const int64_t pitch = blk.pitch;
 
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kg = w >> 2, qw = w & 3;  // key group, 16-query sub-block
@@ -355,16 +308,7 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
     const int l16 = lane & 15, lg = lane >> 4;
     const int prow = lane >> 3, pcol = lane & 7;  // this lane's row / position in a 1-KiB piece
 
-    auto key_row = [&](int kk) -> const T* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs + h * D;
-    };
-    const int nkt = (Lk + KB - 1) / KB, nr = (nkt + KG - 1) / KG;
+    const int nkt = blk.nkt(), nr = (nkt + KG - 1) / KG;
     // Tile t into slot t % NS: its 16 pieces (8 K, 8 V) are dealt over the waves (piece w + i*NWV).
     auto issue_tile = [&](int t) {
         MMT_ATTN_ASSERT(t >= 0 && t < nkt);
@@ -373,7 +317,7 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
         for (int i = 0; i < (16 + NWV - 1) / NWV; ++i) {
             const int piece = w + i * NWV, isv = piece >> 3, pk = piece & 7, r = pk * 8 + prow;
             if (piece >= 16) break;  // wave-uniform
-            const T* src = key_row(min(t * KB + r, Lk - 1)) + (isv ? 2 * C : C);
+            const T* src = blk.key_row(min(t * KB + r, Lk - 1)) + h * D + (isv ? 2 * C : C);
             const int sw = isv ? (pcol ^ (prow & 6)) : (pcol ^ prow);
             attn_glds16(src + sw * 8, slot + isv * KB * 128 + pk * 1024);
         }
@@ -386,9 +330,7 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
     if (w < 8) {
 #pragma unroll
         for (int i = 0; i < (NWV >= 8 ? 1 : 8 / NWV); ++i) {
-            const int piece = NWV >= 8 ? w : w * (8 / NWV) + i, r = piece * 8 + prow;
-            const T* src = qkv + ((int64_t)s * pitch + min(q0 + r, qend - 1)) * rs + h * D;
-            attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);
+            attn_issue_q(blk, h, qimg, NWV >= 8 ? w : w * (8 / NWV) + i, prow, pcol);
         }
     }
     // the whole stream when it fits the ring (no slot reuse), else R - 1 rounds ahead of the consumer
@@ -582,20 +524,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE + FQ * 128];
     char* qimg = lds + FNS * FTILE;
 
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;  // rows between sequences
-    const int nqb_t = (n_t + FQ - 1) / FQ;
     int bx, h, s;
-    attn_block_ids(bx, h, s);
-    const int qb = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qb < nqb_t;
-    const int q0 = tmpl ? qb * FQ : n_t + (qb - nqb_t) * FQ;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const T* qkv = (const T*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
+    attn_block_ids<false>(bx, h, s);
+    const MamBlock<T, FQ> blk(p, bx, s);
+    const int ntok = p.ntok, C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
+    const int64_t pitch = blk.pitch;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int l16 = lane & 15, lg = lane >> 4;
@@ -606,42 +539,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     // pk*8 + prow of the tile, this lane's swizzled 16-B chunk.
     const int isv = w >> 1;
     const int64_t col = (isv ? 2 * C : C) + h * D + (isv ? (pcol ^ (prow & 6)) : (pcol ^ prow)) * 8;
-    auto key_row = [&](int kk) -> const T* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs;
-    };
-    const bool aligned = n_t % KB == 0;  // every tile lies in one key segment
-    const int nkt = (Lk + KB - 1) / KB;
+    // (This tile issue is written out in the fa, lz and lz2 kernels, which differ in the pieces per wave:
+    // as a shared function it compiles to different code, fewer registers included, and these kernels are
+    // kept instruction-identical across refactors.)
+    const bool aligned = blk.aligned();  // every full tile lies in one key segment
+    const int nkt = blk.nkt();
     auto issue_tile = [&](int t) {
         MMT_ATTN_ASSERT(t >= 0 && t < nkt);
         char* slot = lds + (t % FNS) * FTILE + isv * KB * 128;
         if (aligned && t * KB + KB <= Lk) {
-            const T* base = key_row(t * KB);  // wave-uniform
+            const T* base = blk.key_row(t * KB);  // wave-uniform
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int pk = (w & 1) * 4 + i;
-                attn_glds16(base + (int64_t)(pk * 8 + prow) * rs + col, slot + pk * 1024);
+                attn_glds16(base + (int64_t)(pk * 8 + prow) * blk.rs + col, slot + pk * 1024);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int pk = (w & 1) * 4 + i;
-                attn_glds16(key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
+                attn_glds16(blk.key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
             }
         }
     };
     // Q image: 128 rows (16 pieces, 4 per wave); rows past the block's end re-read the last query
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int piece = w * 4 + i, r = piece * 8 + prow;
-        const T* src = qkv + ((int64_t)s * pitch + min(q0 + r, qend - 1)) * rs + h * D;
-        attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);
-    }
+    for (int i = 0; i < 4; ++i) attn_issue_q(blk, h, qimg, w * 4 + i, prow, pcol);
     for (int t = 0; t < FNS - 1 && t < nkt; ++t) issue_tile(t);
 
     const bool active = q0 + 32 * w < qend;  // wave-uniform: this wave has queries
@@ -832,20 +755,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     const mmt_attn_params p) {
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE];
 
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;  // rows between sequences
-    const int nqb_t = (n_t + FQ - 1) / FQ;
+    MamBlock<bf16_t, FQ> blk(p);
     int bx, h, s;
-    attn_block_ids_xcd(bx, h, s);
-    const int qb = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qb < nqb_t;
-    const int q0 = tmpl ? qb * FQ : n_t + (qb - nqb_t) * FQ;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const bf16_t* qkv = (const bf16_t*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
+    attn_block_ids<true>(bx, h, s);
+    blk.place(p, bx, s);
+    const int ntok = p.ntok, C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
+    const int64_t pitch = blk.pitch;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int l32 = lane & 31, hf = lane >> 5;
@@ -854,32 +769,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     // ---- K / V DMA (waves 0-1: K, 2-3: V), 4 pieces of 8 rows x 128 B per wave per tile
     const int isv = w >> 1;
     const int64_t col = (isv ? 2 * C : C) + h * D + (isv ? (pcol ^ attn_vswz(prow)) : (pcol ^ prow)) * 8;
-    auto key_row = [&](int kk) -> const bf16_t* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs;
-    };
-    const bool aligned = n_t % KB == 0;  // every full tile lies in one key segment
-    const int nkt = (Lk + KB - 1) / KB;
+    const bool aligned = blk.aligned();
+    const int nkt = blk.nkt();
     auto issue_tile = [&](int t) {
         MMT_ATTN_ASSERT(t >= 0 && t < nkt);
         char* slot = lds + (t % FNS) * FTILE + isv * KB * 128;
         if (aligned && t * KB + KB <= Lk) {
-            const bf16_t* base = key_row(t * KB);  // wave-uniform
+            const bf16_t* base = blk.key_row(t * KB);  // wave-uniform
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int pk = (w & 1) * 4 + i;
-                attn_glds16(base + (int64_t)(pk * 8 + prow) * rs + col, slot + pk * 1024);
+                attn_glds16(base + (int64_t)(pk * 8 + prow) * blk.rs + col, slot + pk * 1024);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int pk = (w & 1) * 4 + i;
-                attn_glds16(key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
+                attn_glds16(blk.key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
             }
         }
     };
@@ -887,11 +793,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     // slot: read into registers at the first tile, before that slot's first refill
     char* qimg = lds + (FNS - 1) * FTILE;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int piece = w * 4 + i, r = piece * 8 + prow;
-        const bf16_t* src = qkv + ((int64_t)s * pitch + min(q0 + r, qend - 1)) * rs + h * D;
-        attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);
-    }
+    for (int i = 0; i < 4; ++i) attn_issue_q(blk, h, qimg, w * 4 + i, prow, pcol);
     for (int t = 0; t < FNS - 1 && t < nkt; ++t) issue_tile(t);
 
     const bool active = q0 + 32 * w < qend;  // wave-uniform: this wave has queries
@@ -1113,12 +1015,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     // come straight from global memory.  Rare by construction (|log2-scores| ~ 100).
     float qv[32], acc[32];
     {
-        const bf16_t* qp = qkv + ((int64_t)s * pitch + qc) * rs + h * D + 32 * hf;
+        const bf16_t* qp = blk.qkv + ((int64_t)s * pitch + qc) * blk.rs + h * D + 32 * hf;  // (= blk.q_row(q))
 #pragma unroll
         for (int i = 0; i < 32; ++i) qv[i] = bf2f(qp[i]) * cexp;
     }
     auto score = [&](int kk) {
-        const bf16_t* kp = key_row(kk) + C + h * D + 32 * hf;
+        const bf16_t* kp = blk.key_row(kk) + C + h * D + 32 * hf;
         float d0 = 0.f;
 #pragma unroll
         for (int i = 0; i < 32; ++i) d0 += qv[i] * bf2f(kp[i]);
@@ -1132,7 +1034,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     for (int kk = 0; kk < Lk; ++kk) {
         const float e = __builtin_amdgcn_exp2f(score(kk) - m);
         lf += e;
-        const bf16_t* vp = key_row(kk) + 2 * C + h * D + 32 * hf;
+        const bf16_t* vp = blk.key_row(kk) + 2 * C + h * D + 32 * hf;
 #pragma unroll
         for (int i = 0; i < 32; ++i) acc[i] += e * bf2f(vp[i]);
     }
@@ -1163,18 +1065,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // static order measured no faster: profiles/r03_attn_persistent_ab.jsonl.)
 template <int FNS, bool SPLIT = true, bool PIPE2 = true>
 MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, const int h, const int s) {
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;
-    const int nqb_t = (n_t + FQ - 1) / FQ;
-    const int qb0 = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qb0 < nqb_t;
-    const int q0 = tmpl ? qb0 * FQ : n_t + (qb0 - nqb_t) * FQ;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const bf16_t* qkv = (const bf16_t*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
+    const MamBlock<bf16_t, FQ> blk(p, bx, s);
+    const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
+    const int64_t pitch = blk.pitch;
 
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, hf = lane >> 5;
@@ -1182,36 +1075,23 @@ MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, con
 
     const int isv = w;  // wave 0: K pieces, wave 1: V pieces
     const int64_t col = (isv ? 2 * C : C) + h * D + (isv ? (pcol ^ attn_vswz(prow)) : (pcol ^ prow)) * 8;
-    auto key_row = [&](int kk) -> const bf16_t* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs;
-    };
-    const bool aligned = n_t % KB == 0;
-    const int nkt = (Lk + KB - 1) / KB;
+    const bool aligned = blk.aligned();
+    const int nkt = blk.nkt();
     auto issue_tile = [&](int t) {
         MMT_ATTN_ASSERT(t >= 0 && t < nkt);
         char* slot = lds + (t % FNS) * FTILE + isv * KB * 128;
         if (aligned && t * KB + KB <= Lk) {
-            const bf16_t* base = key_row(t * KB);
+            const bf16_t* base = blk.key_row(t * KB);  // wave-uniform
 #pragma unroll
-            for (int pk = 0; pk < 8; ++pk) attn_glds16(base + (int64_t)(pk * 8 + prow) * rs + col, slot + pk * 1024);
+            for (int pk = 0; pk < 8; ++pk) attn_glds16(base + (int64_t)(pk * 8 + prow) * blk.rs + col, slot + pk * 1024);
         } else {
 #pragma unroll
-            for (int pk = 0; pk < 8; ++pk) attn_glds16(key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
+            for (int pk = 0; pk < 8; ++pk) attn_glds16(blk.key_row(min(t * KB + pk * 8 + prow, Lk - 1)) + col, slot + pk * 1024);
         }
     };
     char* qimg = lds + (FNS - 1) * FTILE;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int piece = w * 8 + i, r = piece * 8 + prow;
-        const bf16_t* src = qkv + ((int64_t)s * pitch + min(q0 + r, qend - 1)) * rs + h * D;
-        attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);
-    }
+    for (int i = 0; i < 8; ++i) attn_issue_q(blk, h, qimg, w * 8 + i, prow, pcol);
     for (int t = 0; t < FNS - 1 && t < nkt; ++t) issue_tile(t);
 
     const int qbase = q0 + 64 * w;  // query blocks qbase + 32 qb + [0, 32)
@@ -1436,14 +1316,13 @@ MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, con
                 continue;
             }
             float qv[32], acc[32];
-            const int qc = min(q, qend - 1);
             {
-                const bf16_t* qp = qkv + ((int64_t)s * pitch + qc) * rs + h * D + 32 * hf;
+                const bf16_t* qp = blk.q_row(q) + h * D + 32 * hf;
 #pragma unroll
                 for (int i = 0; i < 32; ++i) qv[i] = bf2f(qp[i]) * cexp;
             }
             auto score = [&](int kk) {
-                const bf16_t* kp = key_row(kk) + C + h * D + 32 * hf;
+                const bf16_t* kp = blk.key_row(kk) + C + h * D + 32 * hf;
                 float d0 = 0.f;
 #pragma unroll
                 for (int i = 0; i < 32; ++i) d0 += qv[i] * bf2f(kp[i]);
@@ -1457,7 +1336,7 @@ MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, con
             for (int kk = 0; kk < Lk; ++kk) {
                 const float e = __builtin_amdgcn_exp2f(score(kk) - m);
                 lf += e;
-                const bf16_t* vp = key_row(kk) + 2 * C + h * D + 32 * hf;
+                const bf16_t* vp = blk.key_row(kk) + 2 * C + h * D + 32 * hf;
 #pragma unroll
                 for (int i = 0; i < 32; ++i) acc[i] += e * bf2f(vp[i]);
             }
@@ -1488,372 +1367,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const mmt_attn_params p) {
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE];
     int bx, h, s;
-    attn_block_ids_xcd(bx, h, s);
+    attn_block_ids<true>(bx, h, s);
     mam_lz2_item<FNS>(p, lds, bx, h, s);
 }
-
-#ifndef MMT_ATTN_AB
-#define MMT_ATTN_AB 0  // A/B build only (tools/build_ablate.sh ab): impl 23
-#endif
-#if MMT_ATTN_AB
-// ---- impl 23: block-pipelined range-checked kernel with a hand-placed issue order ---------------------
-// The same math per 32-key block as impl 17 / 22 (P = exp2(S) with no reference point, row sums on the
-// matrix pipe, epilogue range check with the exact fallback), re-timed so that one wave carries two
-// independent instruction streams at every point of its loop:
-//   slot b, phase 1:  QK^T MFMAs of block b+1 (8)       beside the 32 v_exp_f32 of block b's scores
-//                     and the V^T fragment reads of block b
-//   slot b, phase 2:  PV + row-sum MFMAs of block b (12)  beside the 16 v_cvt_pk of block b and the K
-//                     fragment reads of block b+2
-// i.e. a two-stage software pipeline over 32-key blocks (scores of one block in flight while the
-// previous block is exponentiated and multiplied into O), with sched_group_barrier placing about two
-// exponentials / one pack per MFMA gap (the guide's "<= 24 cycles of issue per 32x32x16 gap").  64
-// queries per wave (two 32-query blocks share every K / V fragment), NW waves per workgroup sharing one
-// K / V stream (NW = 4: 256 queries, half the L2 -> LDS fill of 128-query workgroups), 2 waves per SIMD.
-// K / V tiles: a 4-slot LDS-DMA ring, one barrier per 64-key tile placed inside the slot that first
-// reads the tile; tile t + 2 is issued there into the slot of tile t - 2, which every wave has finished
-// reading (the fragment reads run one block ahead of the math).  Loop: global memory sees only the
-// LDS-DMA pieces, so the counted vmcnt waits never include a store (stores start in the epilogue).
-template <int NW, int WPE = 2>  // waves per workgroup, waves per SIMD (1: the whole 512-register file)
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void mam_attention_hs_kernel(
-    const mmt_attn_params p) {
-    constexpr int R = 4;          // K / V tile slots
-    constexpr int QWG = 64 * NW;  // queries per workgroup
-    constexpr int NP = 16 / NW;   // 1-KiB DMA pieces per wave per tile (8 K + 8 V pieces)
-    static_assert(QWG * 128 <= 2 * FTILE, "the Q image fits the last two ring slots");
-    __shared__ __attribute__((aligned(1024))) char lds[R * FTILE];
-
-    const int n_t = p.n_t, ntok = p.ntok, C = p.C;
-    const int64_t pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;
-    const int nqb_t = (n_t + QWG - 1) / QWG;
-    int bx, h, s;
-    attn_block_ids_xcd(bx, h, s);
-    const int qbk = bx + (p.q_part == 2 ? nqb_t : 0);
-    const bool tmpl = qbk < nqb_t;
-    const int q0 = tmpl ? qbk * QWG : n_t + (qbk - nqb_t) * QWG;
-    const int qend = tmpl ? n_t : ntok;
-    const int Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
-    const bool cross = p.asym && !tmpl;
-    const int64_t rs = 3 * (int64_t)C;
-    const bf16_t* qkv = (const bf16_t*)p.qkv;
-    const int sV = s % p.Bm, sI = sV + p.Bm;
-
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l32 = lane & 31, hf = lane >> 5;
-    const int prow = lane >> 3, pcol = lane & 7;
-
-    auto key_row = [&](int kk) -> const bf16_t* {
-        int seq = s, row = kk;
-        if (cross) {
-            if (kk < n_t) seq = sV;
-            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
-            else row = kk - n_t;
-        }
-        return qkv + ((int64_t)seq * pitch + row) * rs;
-    };
-    const bool aligned = n_t % KB == 0;
-    const int nkt = (Lk + KB - 1) / KB;
-    // wave w DMAs pieces w*NP .. w*NP+NP-1 of a tile: pieces 0-7 = K rows 8i..8i+7, 8-15 = V rows
-    const int isv = (w * NP) >> 3;  // wave-uniform: a wave's pieces are all K or all V
-    const int64_t col = (isv ? 2 * C : C) + h * D + (isv ? (pcol ^ attn_vswz(prow)) : (pcol ^ prow)) * 8;
-    auto issue_tile = [&](int t) {
-        MMT_ATTN_ASSERT(t >= 0 && t < nkt);
-        char* slot = lds + (t % R) * FTILE + isv * KB * 128;
-        if (aligned && t * KB + KB <= Lk) {
-            const bf16_t* base = key_row(t * KB);  // wave-uniform
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int r8 = (w * NP + i) & 7;
-                attn_glds16(base + (int64_t)(r8 * 8 + prow) * rs + col, slot + r8 * 1024);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int r8 = (w * NP + i) & 7;
-                attn_glds16(key_row(min(t * KB + r8 * 8 + prow, Lk - 1)) + col, slot + r8 * 1024);
-            }
-        }
-    };
-    // Q image (QWG rows x 128 B, rows past the block's end re-read the last query) in the last two
-    // slots, read into registers before those slots take tiles 2 and 3
-    char* qimg = lds + (R - 2) * FTILE;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int r = 64 * w + 8 * i + prow;
-        const bf16_t* src = qkv + ((int64_t)s * pitch + min(q0 + r, qend - 1)) * rs + h * D;
-        attn_glds16(src + ((pcol ^ prow) * 8), qimg + (8 * w + i) * 1024);
-    }
-    for (int t = 0; t < 2 && t < nkt; ++t) issue_tile(t);
-
-    const int qbase = q0 + 64 * w;  // query blocks qbase + 32 qb + [0, 32)
-    const bool active = qbase < qend;
-    const float cexp = p.scale * 1.4426950408889634f;
-    const bool prescale = fabsf(cexp - 1.f) > 1e-6f;
-    const float one_or_zero = (((lane & 15) >> 2) & 1) == ((lane >> 4) & 1) ? 1.f : 0.f;
-    const uint32_t sel_w = pack_bf16x2(one_or_zero, one_or_zero);
-    const bf16x8 sel = __builtin_bit_cast(bf16x8, u32x4{sel_w, sel_w, sel_w, sel_w});
-    const int kpos = (l32 & 7) * 16;
-    const int li = lane & 15, qr = li >> 2, pc = li & 3, dsub = (lane >> 4) & 1;
-
-    u32x4 qf[2][4];
-    attn_wait_vm<0>();
-    lds_barrier();
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const int row = 64 * w + 32 * qb + l32;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[qb][ks] = *(const u32x4*)(qimg + row * 128 + (((2 * ks + hf) ^ (row & 7)) * 16));
-            if (prescale) {
-                u32x4 v = qf[qb][ks];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    v[e] = pack_bf16x2(__uint_as_float(v[e] << 16) * cexp, __uint_as_float(v[e] & 0xffff0000u) * cexp);
-                qf[qb][ks] = v;
-            }
-        }
-    }
-    lds_barrier();
-    for (int t = 2; t < R && t < nkt; ++t) issue_tile(t);
-
-    const int nb = (Lk + 31) / 32;       // 32-key blocks; the last holds Lk - 32 (nb - 1) keys
-    const int nvl = Lk - 32 * (nb - 1);  // valid keys of the last block
-    // LDS fragment reads (inline asm: invisible to hipcc's wait-count tracking, so that it does not
-    // drain the LDS-DMA ring before them; the waits below are explicit)
-    auto kread = [&](int b, u32x4 (&kf)[4]) {
-        const char* krow = lds + ((b >> 1) % R) * FTILE + (32 * (b & 1) + l32) * 128;
-        const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)krow;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const uint32_t ak = a + ((((2 * ks + hf) * 16) ^ kpos));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(kf[ks]) : "v"(ak));
-        }
-    };
-    auto vread = [&](int b, uint2 (&vt)[2][2][2]) {
-        const char* vimg = lds + ((b >> 1) % R) * FTILE + KB * 128;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int row = 32 * (b & 1) + 16 * j + 4 * hf + qr;
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const char* b1 = vimg + row * 128 + (((4 * db + 2 * dsub + (pc >> 1)) ^ attn_vswz(row)) * 16) + (pc & 1) * 8;
-                vt[j][db][0] = attn_tr16<0>(b1);
-                vt[j][db][1] = attn_tr16<8 * 128>(b1);
-            }
-        }
-    };
-    // tile sync point X_t, in step (2t - 1, 0) before the first reads of tile t (K of block 2t): its
-    // pieces landed (own: counted vmcnt; every wave's: the barrier), and every wave is past step
-    // (2t - 2, 1), i.e. past the last reads of tile t - 2 (V^T of block 2t - 3, step (2t - 3, 0)), whose
-    // slot then takes tile t + 2
-    auto sync_tile = [&](int t) {
-        if (t < 2 || t >= nkt) return;  // tiles 0 / 1 landed in the prologue
-        attn_wait_dyn(t + 1 < nkt ? NP : 0);
-        lds_barrier();
-        if (t + 2 < nkt) issue_tile(t + 2);
-    };
-
-    f32x16 o[2][2];
-    f32x4 lacc[2];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o[qb][0][r] = 0.f; o[qb][1][r] = 0.f; }
-        lacc[qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    // Pipeline unit u = (32-key block b, query block qb), in the order (0,0), (0,1), (1,0), ...; step u
-    // issues the MFMAs of PV(u - 1) (4 + 2 row-sum) and QK^T(u + 1) (4) beside the 16 exponentials
-    // and 8 packs of unit u: 288 matrix-pipe cycles against ~240 issue cycles, with two score and two
-    // P buffers live (S(u), S(u + 1); P(u - 1), P(u)).  K fragments change every second step (read
-    // after the QK^T MFMAs of step (b, 0) that last use K(b)), V^T fragments likewise (read after
-    // the PV MFMAs of step (b, 0) that last use V(b - 1)).
-    f32x16 sc[2];    // raw scores / exponentials of the two query blocks
-    u32x4 pf[2][2];  // packed P of the two query blocks, [qb][16-key half]
-    u32x4 kf[4];
-    uint2 vt[2][2][2];
-    auto qk = [&](int qb) {  // scores of query block qb against the block whose K fragments are in kf
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            sc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[ks]),
-                                                             __builtin_bit_cast(bf16x8, qf[qb][ks]),
-                                                             ks ? sc[qb] : f32x16{}, 0, 0, 0);
-    };
-    auto pv = [&](int qb) {  // O += V^T P^T and the row sums, query block qb, block in vt / pf[qb]
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const bf16x8 pb = __builtin_bit_cast(bf16x8, pf[qb][j]);
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const uint2 ua = vt[j][db][0], ub = vt[j][db][1];
-                o[qb][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                    __builtin_bit_cast(bf16x8, make_uint4(ua.x, ua.y, ub.x, ub.y)), pb, o[qb][db], 0, 0, 0);
-            }
-            lacc[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sel, pb, lacc[qb], 0, 0, 0);
-        }
-        if constexpr (WPE == 1) {  // O and the row sums live in the accumulator registers
-            asm volatile("" : "+a"(o[qb][0]), "+a"(o[qb][1]), "+a"(lacc[qb]));
-        }
-    };
-    // P = exp2(S) (keys past Lk: 0) of accumulator elements [r0, r1) of query block qb, packed to bf16
-    // (r0, r1 multiples of 2: whole packed pairs)
-    auto softmax = [&](int qb, bool mask, int r0, int r1) {
-        for (int r = r0; r < r1; ++r) {
-            const float e = __builtin_amdgcn_exp2f(sc[qb][r]);
-            sc[qb][r] = !mask || 8 * (r >> 2) + 4 * hf + (r & 3) < nvl ? e : 0.f;
-        }
-        for (int r = r0; r < r1; r += 2) pf[qb][r >> 3][(r & 7) >> 1] = pack_bf16x2(sc[qb][r], sc[qb][r + 1]);
-    };
-    // the issue pattern of one step: MFMAs each followed by 2 exponentials and 1 pack / select, the
-    // last ones bare (the ~24 issue cycles per 32x32x16 gap of MI355X_MICROARCH.md)
-    auto interleave = [&](int nmfma) {
-        for (int i = 0; i < nmfma; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-            if (i < 8) {
-                __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);  // 2 transcendental (v_exp)
-                __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);  // 1 VALU (pack / select)
-            }
-        }
-    };
-    // an empty asm that takes query block qb's packed P: its exponentials and packs are computed inside
-    // the step's scheduling region (hipcc otherwise sinks them into the next basic block, out of reach
-    // of the region's sched_group_barrier pattern)
-    auto pin = [&](int qb) { asm volatile("" : "+v"(pf[qb][0]), "+v"(pf[qb][1])); };
-    // step (b, 0): PV(b - 1, 1), QK^T(b, 1), softmax(b, 0); reads V(b)
-    auto step0 = [&](int b, auto FIRSTc, auto MASKc) {
-        constexpr bool FIRST = decltype(FIRSTc)::value, MASK = decltype(MASKc)::value;
-        attn_lds_wait();  // V(b - 1) fragments (the sched barrier keeps their consumers below)
-        if constexpr (!FIRST) pv(1);
-        vread(b, vt);  // the previous V^T fragments are consumed by the MFMAs above
-        qk(1);
-        softmax(0, MASK, 0, 16);
-        interleave(FIRST ? 4 : 10);
-        pin(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // step (b, 1): PV(b, 0), QK^T(b + 1, 0), softmax(b, 1); reads K(b + 1) at its start (after the
-    // sync point of a new tile), waited for just before the QK^T MFMAs that need them (the six PV /
-    // row-sum MFMAs cover the read latency)
-    auto step1 = [&](int b, auto LASTc, auto MASKc) {
-        constexpr bool LAST = decltype(LASTc)::value, MASK = decltype(MASKc)::value;
-        if constexpr (!LAST) {
-            if (b & 1) sync_tile((b + 1) / 2);  // first reads of tile (b + 1) / 2
-            kread(b + 1, kf);
-        }
-        // V(b) (read in step (b, 0)): every LDS read but the four K reads just issued (LDS reads
-        // return in order)
-        if constexpr (!LAST) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        pv(0);
-        softmax(1, MASK, 0, 12);
-        interleave(6);
-        pin(1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!LAST) attn_lds_wait();  // K(b + 1)
-        if constexpr (!LAST) qk(0);
-        softmax(1, MASK, 12, 16);
-        if constexpr (!LAST) interleave(4);
-        pin(1);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    using I0 = attn_ic<0>;
-    using I1 = attn_ic<1>;
-
-    if (active) {
-        kread(0, kf);
-        attn_lds_wait();
-        qk(0);
-        const bool mask = nvl < 32;  // the last block holds keys past Lk
-        if (nb == 1) {
-            step0(0, I1{}, I1{});
-            step1(0, I1{}, I1{});
-        } else {
-            step0(0, I1{}, I0{});
-            step1(0, I0{}, I0{});
-            for (int b = 1; b < nb - 1; ++b) {
-                step0(b, I0{}, I0{});
-                step1(b, I0{}, I0{});
-            }
-            if (mask) {
-                step0(nb - 1, I0{}, I1{});
-                step1(nb - 1, I1{}, I1{});
-            } else {
-                step0(nb - 1, I0{}, I0{});
-                step1(nb - 1, I1{}, I0{});
-            }
-        }
-        pv(1);  // the last unit's PV
-    } else {  // no queries: keep the DMA and barrier schedule of the workgroup
-        for (int b = 1; b < nb; b += 2) sync_tile((b + 1) / 2);
-        return;
-    }
-
-    // per query block: range check, normalise and store, or the exact fallback (as impl 22)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const float l = lacc[qb][0];
-        float chk = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) chk += o[qb][0][r] * 0.f + o[qb][1][r] * 0.f;
-        const bool ok = l >= LZ_LO && l <= LZ_HI && chk == 0.f;
-        const int q = qbase + 32 * qb + l32;
-        bf16_t* op = (bf16_t*)p.out + attn_out_row(p, s, q, pitch) * C + h * D;
-        if (__builtin_expect(__all(ok), 1)) {
-            const float inv = 1.f / l;
-            if (q < qend) {
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        *(uint2*)(op + 32 * db + 8 * g + 4 * hf) =
-                            make_uint2(pack_bf16x2(o[qb][db][4 * g] * inv, o[qb][db][4 * g + 1] * inv),
-                                       pack_bf16x2(o[qb][db][4 * g + 2] * inv, o[qb][db][4 * g + 3] * inv));
-            }
-            continue;
-        }
-        float qv[32], acc[32];
-        const int qc = min(q, qend - 1);
-        {
-            const bf16_t* qp = qkv + ((int64_t)s * pitch + qc) * rs + h * D + 32 * hf;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) qv[i] = bf2f(qp[i]) * cexp;
-        }
-        auto score = [&](int kk) {
-            const bf16_t* kp = key_row(kk) + C + h * D + 32 * hf;
-            float d0 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) d0 += qv[i] * bf2f(kp[i]);
-            return d0 + __shfl_xor(d0, 32, 64);
-        };
-        float m = -INFINITY;
-        for (int kk = 0; kk < Lk; ++kk) m = fmaxf(m, score(kk));
-        float lf = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) acc[i] = 0.f;
-        for (int kk = 0; kk < Lk; ++kk) {
-            const float e = __builtin_amdgcn_exp2f(score(kk) - m);
-            lf += e;
-            const bf16_t* vp = key_row(kk) + 2 * C + h * D + 32 * hf;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) acc[i] += e * bf2f(vp[i]);
-        }
-        if (q < qend) {
-            const float inv = 1.f / lf;
-#pragma unroll
-            for (int i = 0; i < 32; i += 8)
-                *(u32x4*)(op + 32 * hf + i) = u32x4{pack_bf16x2(acc[i] * inv, acc[i + 1] * inv), pack_bf16x2(acc[i + 2] * inv, acc[i + 3] * inv),
-                                                    pack_bf16x2(acc[i + 4] * inv, acc[i + 5] * inv), pack_bf16x2(acc[i + 6] * inv, acc[i + 7] * inv)};
-        }
-    }
-}
-#endif  // MMT_ATTN_AB
 
 }  // namespace
 
 int mmt_attn_launch_ps(const mmt_attn_params& p, hipStream_t st);  // attention_ps.hip: impl 29 (persistent)
-#if MMT_ATTN_AB
-int mmt_attn_launch_pp(const mmt_attn_params& p, int ks, hipStream_t st);  // attention_pp.hip: impl 24 / 25
-int mmt_attn_launch_pg(const mmt_attn_params& p, hipStream_t st);          // attention_pg.hip: impl 28
-#endif
 
 namespace {
 
@@ -1861,11 +1381,11 @@ template <typename T>
 int launch_attn(const mmt_attn_params& p, hipStream_t st) {
     // impl: 0 = the library's choice by dtype and grid size; forced (A/B and tests): 4 = latency kernel,
     // 8 = running-maximum throughput kernel, 17 / 21 / 22 = range-checked exponent kernels (22 = 64
-    // queries per wave); A/B build: 23 = the block-pipelined form of 22 with 256-query workgroups
-    if (p.impl != 0 && p.impl != 4 && p.impl != 8 && p.impl != 17 && p.impl != 21 && p.impl != 22 && p.impl != 29 &&
-        !(MMT_ATTN_AB && (p.impl == 23 || p.impl == 24 || p.impl == 25 || p.impl == 26 || p.impl == 27 || p.impl == 28)))
+    // queries per wave), 29 = the persistent form of 22.  23-28 were A/B-only experiments, since removed
+    // (header comment): rejected like any unknown impl
+    if (p.impl != 0 && p.impl != 4 && p.impl != 8 && p.impl != 17 && p.impl != 21 && p.impl != 22 && p.impl != 29)
         return MMT_EBADARG;
-    // lse (training forward) is written by impls 0 / 4 / 8 / 17 / 21 only: impls 22 / 23 never write it
+    // lse (training forward) is written by impls 0 / 4 / 8 / 17 / 21 only: impls 22 / 29 never write it
     if (p.lse && (sizeof(T) != 2 || p.impl >= 22)) return MMT_EBADARG;
     // fp16: the kernels with a running maximum (latency kernel, throughput kernel); the range-checked
     // exponent kernels are bf16, and the training forward (lse) is bf16
@@ -1916,21 +1436,6 @@ int launch_attn(const mmt_attn_params& p, hipStream_t st) {
             const int rc = mmt_attn_launch_ps(p, st);
             if (rc) return rc;
         }
-#if MMT_ATTN_AB
-        else if (impl == 24 || impl == 25) mmt_attn_launch_pp(p, impl == 25 ? 2 : 1, st);
-        else if (impl == 28) mmt_attn_launch_pg(p, st);
-        else if (impl == 23) {  // block-pipelined kernel, 4 waves (256 queries) per workgroup
-            const int nt = (p.n_t + 255) / 256, ns = (p.ntok - p.n_t + 255) / 256;
-            const dim3 hgrid(p.q_part == 1 ? nt : p.q_part == 2 ? ns : nt + ns, p.H, p.S);
-            hipLaunchKernelGGL((mam_attention_hs_kernel<4>), hgrid, dim3(256), 0, st, p);
-        } else if (impl == 26) {  // the same at one wave per SIMD (one 256-query workgroup per CU)
-            const int nt = (p.n_t + 255) / 256, ns = (p.ntok - p.n_t + 255) / 256;
-            const dim3 hgrid(p.q_part == 1 ? nt : p.q_part == 2 ? ns : nt + ns, p.H, p.S);
-            hipLaunchKernelGGL((mam_attention_hs_kernel<4, 1>), hgrid, dim3(256), 0, st, p);
-        } else if (impl == 27) {  // 2-wave (128-query) workgroups at one wave per SIMD (two per CU)
-            hipLaunchKernelGGL((mam_attention_hs_kernel<2, 1>), fgrid, dim3(128), 0, st, p);
-        }
-#endif
         else if (impl == 8 || p.lse) hipLaunchKernelGGL((mam_attention_fa_kernel<T, 2, 3>), fgrid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((mam_attention_glds_kernel<T, 4>), grid, dim3(1024), 0, st, p);
     } else {  // fp32 (parity path); small grids: 4 waves x 16 queries to occupy more SIMDs

@@ -1,5 +1,6 @@
-// Helpers shared by the MAM attention translation units (attention.hip, attention_pp.hip): tile
-// geometry, the XCD-aware block map, LDS-DMA issue / counted waits, and the LDS fragment reads.
+// Shared by the MAM attention translation units (attention.hip, attention_ps.hip): the query-block
+// geometry and the asymmetric key mapping (MamBlock / MamKeys: which keys a query block sees), the XCD-aware block
+// map, LDS-DMA issue / counted waits, and the LDS fragment reads.
 #pragma once
 #include "common.hpp"
 
@@ -27,11 +28,24 @@ struct attn_ic {
     static constexpr int value = N;
 };
 
-// XCD-aware bijective block remap at every grid size: each XCD gets a contiguous run of (query
-// block, head, sequence) ids, query block fastest, so the query blocks of one (sequence, head)
-// re-read its K / V rows from one L2.
-MMT_DEV void attn_block_ids_xcd(int& bx, int& by, int& bz) {
+// XCD-aware bijective block remap (as gemm.hip): workgroups are dealt round-robin over the 8 XCDs, so
+// consecutive (query block, head, sequence) ids would put the query blocks of one (sequence, head) on
+// different XCDs, each fetching the same K / V rows into its own L2.  Giving each XCD a contiguous run
+// of ids (query block fastest) keeps those re-reads in one L2.  Speed only.
+// SMALL_GRIDS = false: grids that fit the chip (<= 256 workgroups, batch-1 tracking) keep the identity
+// map (B = 8 / 32 throughput kernel 33 -> 29 / 90 -> 84 us with the remap; the single-wave batch-1 grid
+// gains nothing); true: remapped at every grid size (the range-checked kernels).
+template <bool SMALL_GRIDS>
+MMT_DEV void attn_block_ids(int& bx, int& by, int& bz) {
     const int nbx = gridDim.x, nby = gridDim.y, nwg = nbx * nby * gridDim.z;
+    if constexpr (!SMALL_GRIDS) {
+        if (nwg <= 256) {
+            bx = blockIdx.x;
+            by = blockIdx.y;
+            bz = blockIdx.z;
+            return;
+        }
+    }
     const int orig = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
     const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
     const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
@@ -97,5 +111,82 @@ MMT_DEV int64_t attn_out_row(const mmt_attn_params& p, int s, int q, int64_t pit
 // V image swizzle: chunk c of row r at c ^ (r & 6) ^ ((r & 2) << 1): the 4 rows x 4 chunks a
 // half-wave reads per tr instruction then cover all 64 banks once.
 MMT_DEV int attn_vswz(int row) { return (row & 6) ^ ((row & 2) << 1); }
+
+// The keys one query of sequence s sees, and where they live.  Rows of qkv are rs = 3 C elements
+// (q | k | v), sequences are pitch rows apart.  cross = false: key kk is the sequence's own token kk.
+// cross = true (search queries of the cross-modal form): the asymmetric stream [template V | template I |
+// own search], i.e. keys [0, n_t) are the template of the RGB sequence sV = s % Bm, [n_t, 2 n_t) the
+// template of the TIR sequence sI = sV + Bm, and [2 n_t, ntok + n_t) the own search tokens n_t .. ntok - 1.
+// Row pointers are to the row's start: callers add the k / v and head offsets.
+// (A base of MamBlock, not part of it: merged into one struct the kernels compile to different code.)
+template <typename T>
+struct MamKeys {
+    const T* qkv;
+    int64_t pitch, rs;
+    int n_t, s, sV, sI;
+    bool cross;
+    MMT_DEV const T* key_row(int kk) const {
+        int seq = s, row = kk;
+        if (cross) {
+            if (kk < n_t) seq = sV;
+            else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
+            else row = kk - n_t;
+        }
+        return qkv + ((int64_t)seq * pitch + row) * rs;
+    }
+};
+
+// One query block of the MAM: QB consecutive queries [q0, min(q0 + QB, qend)) of sequence s, all template
+// or all search tokens, and the Lk keys they see.  This is the one statement of that geometry for the
+// forward kernels of attention.hip (attention_ps.hip's item walk and attention_bwd.hip's joint-key decode
+// keep their own forms).  Query blocks are numbered template blocks first (ceil(n_t / QB) of them, the
+// last one short), then search blocks from token n_t; q_part = 2 launches start at the first search
+// block.  Template queries see the sequence's own template keys (Lk = n_t); search queries see every own
+// token (Lk = ntok) or, cross-modal (p.asym), the stream of MamKeys (Lk = ntok + n_t).  Keys are consumed
+// in nkt() tiles of KB; the last may be short.
+template <typename T, int QB>
+struct MamBlock : MamKeys<T> {
+    int ntok, nqb_t, q0, qend, Lk;
+    bool tmpl;
+    MMT_DEV MamBlock(const mmt_attn_params& p, int bx, int s) : MamBlock(p) { place(p, bx, s); }
+    // The same in two steps, the launch-only part first and the block's place after the kernel has read its
+    // block ids (impl 17 / 21 is written in that order and its generated code depends on it); the block
+    // is valid after place().
+    MMT_DEV explicit MamBlock(const mmt_attn_params& p) {
+        this->n_t = p.n_t;
+        ntok = p.ntok;
+        this->pitch = p.tok_pitch > 0 ? p.tok_pitch : ntok;
+        nqb_t = (this->n_t + QB - 1) / QB;
+    }
+    MMT_DEV void place(const mmt_attn_params& p, int bx, int s) {
+        const int n_t = this->n_t;
+        this->s = s;
+        const int qb = bx + (p.q_part == 2 ? nqb_t : 0);
+        tmpl = qb < nqb_t;
+        q0 = tmpl ? qb * QB : n_t + (qb - nqb_t) * QB;
+        qend = tmpl ? n_t : ntok;
+        Lk = tmpl ? n_t : (p.asym ? ntok + n_t : ntok);
+        this->cross = p.asym && !tmpl;
+        this->rs = 3 * (int64_t)p.C;
+        this->qkv = (const T*)p.qkv;
+        this->sV = s % p.Bm;
+        this->sI = this->sV + p.Bm;
+    }
+    MMT_DEV int nkt() const { return (Lk + KB - 1) / KB; }
+    MMT_DEV bool aligned() const { return this->n_t % KB == 0; }  // no full key tile straddles two key segments
+    // query q, clamped to the block's last query (rows past it are staged and computed, never stored)
+    MMT_DEV const T* q_row(int q) const { return this->qkv + ((int64_t)this->s * this->pitch + min(q, qend - 1)) * this->rs; }
+};
+
+// LDS-DMA of one 1-KiB piece of a query block's Q image: query rows 8 piece .. 8 piece + 7 of the block
+// (rows past the block's end re-read its last query), 128 B per row at head h, chunk c of row r stored at
+// c ^ (r & 7); this lane moves chunk pcol of row prow.  (One piece per call: the piece loops stay in the
+// kernels, where moving them into a helper changes the generated code.)
+template <typename T, int QB>
+MMT_DEV void attn_issue_q(const MamBlock<T, QB>& blk, int h, char* qimg, int piece, int prow, int pcol) {
+    const int r = piece * 8 + prow;
+    const T* src = blk.q_row(blk.q0 + r) + h * D;
+    attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);
+}
 
 }  // namespace

@@ -78,11 +78,10 @@ def test_bad_arguments_rejected_without_gpu_work():
 
 
 def test_attention_impl_and_lse_gate():
-    """mmt_mam_attention takes impl 0 (library choice), 4, 8, 17, 21, 22 only (the round-2 A/B-only
-    kernels 2, 9-12, 16, 18-20 are no longer in the library; 23-28 -- incl. round 4's one-wave-per-SIMD
-    impl 24 / 25 and round 5's ping-pong impl 28 -- are in the A/B build only); impl 22 never writes the
-    log-sum-exp
-    the training backward consumes, so lse with them is rejected; fp16 takes the running-maximum kernels
+    """mmt_mam_attention takes impl 0 (library choice), 4, 8, 17, 21, 22 and the opt-in persistent 29 only
+    (the round-2 A/B-only kernels 2, 9-12, 16, 18-20 and the later A/B-only kernels 23-28 -- incl. round 4's
+    one-wave-per-SIMD impl 24 / 25 and round 5's ping-pong impl 28 -- are removed from the source); impl 22
+    never writes the log-sum-exp the training backward consumes, so lse with them is rejected; fp16 takes the running-maximum kernels
     only.  Every case fails validation on the host, before a launch."""
     from mmt_amd import _lib
     fake = 1 << 20  # 16-B aligned, never dereferenced
