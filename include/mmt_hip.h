@@ -230,11 +230,20 @@ typedef struct {
 
 int mmt_mam_attention(const mmt_attn_params* p, int dtype, void* stream);
 
-/* MAM attention backward (training, two-stream / shared layout: asym must be 0; bf16).  qkv / out
- * as in the forward (q NOT pre-scaled: pass the natural `scale`), dout = dL/dout [S][ntok][C], lse
- * from the forward with the same qkv and scale; delta: [S][H][ntok] fp32 workspace; dqkv:
- * [S][ntok][3C] = (dL/dq, dL/dk, dL/dv) in the qkv layout.  Deterministic (no atomics).
- * Replaces the autograd of Attention.forward, mixformer.py:52-78. */
+/* MAM attention backward (training; bf16), of both key layouts of the forward.  qkv / out as in the
+ * forward (q NOT pre-scaled: pass the natural `scale`), dout = dL/dout [S][ntok][C], lse from the
+ * forward with the same qkv, scale and asym; delta: [S][H][ntok] fp32 workspace; dqkv:
+ * [S][ntok][3C] = (dL/dq, dL/dk, dL/dv) in the qkv layout.
+ *   asym == 0 (two-stream / shared layout; any S, Bm ignored): replaces the autograd of
+ *     Attention.forward, mixformer.py:52-78.
+ *   asym == 1 (cross-modal layout, asymmetric_shared.py:55-104): S must equal 2 * Bm (else
+ *     MMT_EBADARG, before any launch), RGB sequences first.  A search query of sequence s attends
+ *     [template of s % Bm | template of s % Bm + Bm | own search], so dK / dV of a template key of
+ *     sequence (m, b) are summed over three query groups, always in this order: its own template
+ *     queries, the search queries of sequence b, the search queries of sequence b + Bm.  A search
+ *     key takes the search queries of its own sequence only.
+ * Deterministic: one wave sums each gradient element in a fixed order (no atomics), and each
+ * element is rounded to bf16 once. */
 typedef struct {
     const void* qkv;
     const void* out;

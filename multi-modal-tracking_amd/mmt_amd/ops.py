@@ -12,6 +12,9 @@ ones carry `register_autograd` formulas built from the registered backward ops:
                                                 mmt_prroi_pool_* (fp32; prroi_pool/functional.py:38-76)
   mmt::mam_attention_forward / _backward        mmt_mam_attention (with log-sum-exp) / mmt_mam_attention_bwd
                                                 (bf16, the training form of mixformer.py:52-78)
+  mmt::mam_attention_asym_forward / _backward   the same pair with asym = 1: the cross-modal form of
+                                                asymmetric_shared.py:55-104 (search queries attend [template V |
+                                                template I | own search]) on (2 Bh, ntok, 3C), RGB sequences first
   mmt::ce_select                                mmt_ce_t2s_attention_masked + mmt_ce_select: the candidate
                                                 elimination's scores and sorted top-k (no autograd formula:
                                                 only indices leave get_token_from_attn,
@@ -249,6 +252,72 @@ def _mam_backward(ctx, dout, dlse):
 mam_attention_forward.register_autograd(_mam_backward, setup_context=_mam_setup)
 
 
+@torch.library.custom_op("mmt::mam_attention_asym_forward", mutates_args=())
+def mam_attention_asym_forward(qkv: torch.Tensor, Bh: int, n_t: int, heads: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """The cross-modal asymmetric form (asymmetric_shared.py:55-104) on qkv [2 Bh][ntok][3C] bf16, the Bh RGB
+    sequences first -> (out [2 Bh][ntok][C] bf16, lse [2 Bh][H][ntok] fp32): template queries attend the template
+    keys of their own sequence, search queries of sequence s attend [template of s % Bh | template of
+    s % Bh + Bh | own search]."""
+    _need(qkv, "qkv", (torch.bfloat16,))
+    S, ntok, C3 = qkv.shape
+    if S != 2 * Bh:
+        raise RuntimeError("mam_attention_asym_forward: qkv (2 Bh, ntok, 3C) expected")
+    C = C3 // 3
+    out = torch.empty(S, ntok, C, device=qkv.device, dtype=torch.bfloat16)
+    lse = torch.empty(S, heads, ntok, device=qkv.device, dtype=torch.float32)
+    p = AttnParams()
+    p.qkv, p.out, p.S, p.Bm, p.ntok, p.n_t, p.C, p.H, p.asym = qkv.data_ptr(), out.data_ptr(), S, Bh, ntok, n_t, C, heads, 1
+    p.scale, p.impl, p.lse = (C // heads) ** -0.5, 0, lse.data_ptr()
+    check(LIB.mmt_mam_attention(p, MMT_BF16, _stream()), "mmt_mam_attention")
+    return out, lse
+
+
+@mam_attention_asym_forward.register_fake
+def _(qkv, Bh, n_t, heads):
+    S, ntok, C3 = qkv.shape
+    return qkv.new_empty(S, ntok, C3 // 3), qkv.new_empty(S, heads, ntok, dtype=torch.float32)
+
+
+@torch.library.custom_op("mmt::mam_attention_asym_backward", mutates_args=())
+def mam_attention_asym_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, Bh: int,
+                                n_t: int, heads: int) -> torch.Tensor:
+    """dL/dqkv [2 Bh][ntok][3C] bf16 of the cross-modal form (deterministic, mmt_mam_attention_bwd with asym = 1):
+    dK / dV of a template key sum its own template queries and the search queries of both modalities."""
+    _need(qkv, "qkv", (torch.bfloat16,))
+    S, ntok, C3 = qkv.shape
+    C = C3 // 3
+    dout = dout.to(torch.bfloat16).contiguous()
+    delta = torch.empty_like(lse)
+    dqkv = torch.empty_like(qkv)
+    p = AttnBwdParams()
+    p.qkv, p.out, p.dout, p.lse, p.delta, p.dqkv = (qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                                    delta.data_ptr(), dqkv.data_ptr())
+    p.S, p.Bm, p.ntok, p.n_t, p.C, p.H, p.asym, p.scale = S, Bh, ntok, n_t, C, heads, 1, (C // heads) ** -0.5
+    check(LIB.mmt_mam_attention_bwd(p, MMT_BF16, _stream()), "mmt_mam_attention_bwd")
+    return dqkv
+
+
+@mam_attention_asym_backward.register_fake
+def _(qkv, out, dout, lse, Bh, n_t, heads):
+    return torch.empty_like(qkv)
+
+
+def _mam_asym_setup(ctx, inputs, output):
+    qkv, Bh, n_t, heads = inputs
+    out, lse = output
+    ctx.args = (Bh, n_t, heads)
+    ctx.save_for_backward(qkv, out, lse)
+
+
+def _mam_asym_backward(ctx, dout, dlse):
+    qkv, out, lse = ctx.saved_tensors
+    Bh, n_t, heads = ctx.args
+    return mam_attention_asym_backward(qkv, out, dout, lse, Bh, n_t, heads), None, None, None
+
+
+mam_attention_asym_forward.register_autograd(_mam_asym_backward, setup_context=_mam_asym_setup)
+
+
 # --------------------------------------------------------------------------- candidate elimination
 @torch.library.custom_op("mmt::ce_select", mutates_args=())
 def ce_select(qkv: torch.Tensor, template_mask: Optional[torch.Tensor], gidx_in: Optional[torch.Tensor], n_t: int,
@@ -363,6 +432,11 @@ ce_rows_gather.register_autograd(_rows_backward, setup_context=_rows_setup)
 def mam_attention(qkv, n_t, heads):
     """Differentiable MAM attention output (bf16): mmt::mam_attention_forward's first output."""
     return mam_attention_forward(qkv.contiguous(), n_t, heads)[0]
+
+
+def mam_attention_asym(qkv, Bh, n_t, heads):
+    """Differentiable cross-modal MAM attention output (bf16): mmt::mam_attention_asym_forward's first output."""
+    return mam_attention_asym_forward(qkv.contiguous(), Bh, n_t, heads)[0]
 
 
 def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):

@@ -532,6 +532,34 @@ class _HipMamAttention(torch.autograd.Function):
         return mam_attention_backward(qkv, out, dout, lse, ctx.n_t, ctx.heads), None, None
 
 
+# The cross-modal attention of the asymmetric models (HipOps.mam_attention_asym) by the native op pair
+# mmt::mam_attention_asym_forward / _backward; False: composed from two standard attentions and torch.cat copies
+# (asym_attention_from_mam, the form before the backward kernels took asym = 1; A/B knob,
+# tools/attn_asym_bwd_time.py)
+ASYM_NATIVE = True
+
+
+class _HipMamAttentionAsym(torch.autograd.Function):
+    """Cross-modal asymmetric MAM attention (asymmetric_shared.py:55-104) over qkv [2 Bh][ntok][3C] bf16, RGB
+    sequences first -> [2 Bh][ntok][C] bf16: the registered ops mmt::mam_attention_asym_forward /
+    mmt::mam_attention_asym_backward.  One forward saves (qkv, out, lse), one backward call gives dqkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, Bh, n_t, heads):
+        from .ops import mam_attention_asym_forward
+        qkv = qkv.contiguous()
+        out, lse = mam_attention_asym_forward(qkv, Bh, n_t, heads)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.Bh, ctx.n_t, ctx.heads = Bh, n_t, heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .ops import mam_attention_asym_backward
+        qkv, out, lse = ctx.saved_tensors
+        return mam_attention_asym_backward(qkv, out, dout, lse, ctx.Bh, ctx.n_t, ctx.heads), None, None, None
+
+
 def _ln_fwd(ctx, x, w0, b0, w1, b1, rows0, eps, out_f32):
     """mmt_layernorm of x (fp32, last dim C) -> [rows][C] bf16 (fp32 with out_f32); saves what _ln_bwd needs."""
     from ._lib import LIB, MMT_BF16, check
@@ -1447,6 +1475,8 @@ class HipOps:
 
     @staticmethod
     def mam_attention_asym(qkv, Bh, n_t, heads):
+        if ASYM_NATIVE:
+            return _HipMamAttentionAsym.apply(qkv, Bh, n_t, heads)
         return asym_attention_from_mam(HipOps.mam_attention, qkv, Bh, n_t, heads)
 
     @staticmethod
