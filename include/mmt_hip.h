@@ -351,7 +351,7 @@ int mmt_ms_deform_attn_backward_impl(const void* value, const int64_t* spatial_s
  * asymmetric_shared_ce.py (CE_Block_Shared :228-282, candidate_elimination :52-102,
  * get_token_from_attn :22-46, _recover_search :426-447).  Token streams are [S][tok_pitch][C]
  * with S = 2*Bm sequences, modality-major; a stage keeps each sequence's first n_t + keep rows.
- *   mmt_ce_t2s_attention: partial[Bm][H][2*n_t/QB][2*n_s] (QB = 16 for MMT_BF16, 8 for MMT_F32)
+ *   mmt_ce_t2s_attention: partial[Bm][H][2*n_t/QB][2*n_s] (QB = 16 for MMT_BF16 / MMT_F16, 8 for MMT_F32)
  *     column sums of the template->search
  *     softmax (qkv [S][tok_pitch][3C], q/k in place; scale in natural-log units, i.e. 1/log2(e)
  *     when q carries scale*log2(e) already);
@@ -367,7 +367,7 @@ int mmt_ms_deform_attn_backward_impl(const void* value, const int64_t* spatial_s
  *   mmt_ce_gather: xc rows [0, n_t + keep) of every sequence = x's template rows then the kept
  *     rows in order (xn, if not NULL, gets the same rows cast to xn_dtype);
  *   mmt_ce_recover: out rows [n_t, n_t + ns_full) = x's surviving rows (slots [0, keep) of the
- *     final gidx) at their original positions, zeros where pruned (dtype MMT_BF16 / MMT_F32);
+ *     final gidx) at their original positions, zeros where pruned (dtype MMT_BF16 / MMT_F16 / MMT_F32);
  * and, for the training forward (packed fp32 streams [S][n_t + lens][C] that shrink at every stage):
  *   mmt_ce_rows_gather: dst[s][r] = src[s][idx[s][r]] for fp32 rows of C values (C % 4 == 0, C <= 1024;
  *     src [S][src_rows][C], dst [S][dst_rows][C], idx [S][dst_rows]); an index outside [0, src_rows) gives
@@ -375,7 +375,13 @@ int mmt_ms_deform_attn_backward_impl(const void* value, const int64_t* spatial_s
  *     and both of their backwards are this call with four index vectors;
  *   mmt_ce_index_invert: idx_out[s][idx_in[s][j]] = j for j < n_in, -1 elsewhere (idx_in [S][n_in],
  *     idx_out [S][n_out], n_out <= 2048; entries outside [0, n_out) are skipped; deterministic for
- *     distinct entries). */
+ *     distinct entries);
+ * and, for the search pass of the template K/V cache (packed streams of search rows only, [S][rows][C]):
+ *   mmt_ce_rows_gather_cast: mmt_ce_rows_gather with two optional outputs, dst (fp32) and dst_t (the same
+ *     rows cast to t_dtype: MMT_BF16 / MMT_F16 / MMT_F32), at least one of them; idx rows are idx_pitch
+ *     entries apart (>= dst_rows; 0 = dst_rows).  With idx = mmt_ce_select's order (idx_pitch = ns_full) it
+ *     is a pruning stage, with idx = mmt_ce_index_invert of the final gidx the recovery (zero rows where
+ *     pruned).  Every destination row is written, nothing else. */
 int mmt_ce_t2s_attention(const void* qkv, float* partial, int Bm, int tok_pitch, int n_t, int n_s, int C, int H,
                          float scale, int dtype, void* stream);
 int mmt_ce_t2s_attention_masked(const void* qkv, float* partial, const unsigned char* template_mask, int Bm,
@@ -389,6 +395,8 @@ int mmt_ce_recover(const float* x, const int* gidx, int keep, void* out, int S, 
 int mmt_ce_rows_gather(const float* src, int src_rows, float* dst, int dst_rows, const int* idx, int S, int C,
                        void* stream);
 int mmt_ce_index_invert(const int* idx_in, int n_in, int* idx_out, int n_out, int S, void* stream);
+int mmt_ce_rows_gather_cast(const float* src, int src_rows, float* dst, void* dst_t, int dst_rows, const int* idx,
+                            int idx_pitch, int S, int C, int t_dtype, void* stream);
 
 /* Bimodal encoder layer core (ms_deform_attn_bimodal.py:97-128) for nq queries per modality on an
  * hw x hw map, 8 heads x 64 ch, 2 levels x 4 points: offw[b*nq+q][192] fp32 = [sampling_offsets

@@ -17,7 +17,7 @@
 // attention run on those rows (row maps / mmt_attn_params.tok_pitch).
 //
 //   mmt_ce_t2s_attention  partial column sums of attn_t2s: one workgroup per (16 template queries
-//                         (bf16, MFMA scores) or 8 (fp32, VALU), head, frame), scores from the qkv rows
+//                         (bf16 / fp16, MFMA scores) or 8 (fp32, VALU), head, frame), scores from the qkv rows
 //                         in place, softmax per query row in LDS, the rows summed per key ->
 //                         partial[b][h][qblock][2k]; with a template mask ([b][2 n_t] bytes, query
 //                         order [q_mt_V ; q_mt_I]) a row enters the sum times its 0 / 1 mask value, and
@@ -38,6 +38,12 @@
 //   mmt_ce_rows_gather    fp32 rows src [S][src_rows][C] -> dst [S][dst_rows][C] by idx [S][dst_rows]
 //                         (an index outside [0, src_rows) is a zero row and is never dereferenced)
 //   mmt_ce_index_invert   idx_out[s][idx_in[s][j]] = j, -1 elsewhere: the backward's index vector
+//
+// Template K/V cache (runtime.py cache_workspace, the search pass): the streams hold only the search rows,
+// packed [S][k][C], and shrink at every stage as in training; the pruning and the recovery are
+//   mmt_ce_rows_gather_cast  the same indexed row copy writing the fp32 rows and / or their copy in the
+//                            GEMM operand type (bf16 / fp16 / fp32); idx = the order vector (pruning) or
+//                            the inverted final gidx (recovery: zero rows where pruned)
 #include "common.hpp"
 
 namespace {
@@ -162,8 +168,8 @@ __global__ __launch_bounds__(256) void ce_t2s_kernel(const T* __restrict__ qkv, 
     }
 }
 
-// bf16 path: the scores of 16 template queries by MFMA, kept in registers.  S^T [16 keys][16
-// queries] blocks = K Q^T with v_mfma_f32_16x16x32_bf16 (A = key rows, B = query rows, 16-B
+// 16-bit path (bf16 / fp16): the scores of 16 template queries by MFMA, kept in registers.  S^T [16 keys][16
+// queries] blocks = K Q^T with v_mfma_f32_16x16x32_bf16 / _f16 (A = key rows, B = query rows, 16-B
 // fragments read straight from the qkv rows, all of a wave's key blocks loaded up front); lane l
 // holds query l%16 against keys 4*(l/16)..+3 of each block.  Row max / sum: over the lane's values,
 // the 4 lanes of the query (permlane swaps) and the 4 waves (LDS); column sums over the 16 queries:
@@ -178,7 +184,8 @@ MMT_DEV float ce_row16_sum(float v) {
     return v;
 }
 constexpr int CE_QBM = 16, CE_MAXI = 18;  // key blocks per wave: 2k <= 4 * 18 * 16 = 1152 (ViT-L 384 px)
-__global__ __launch_bounds__(256) void ce_t2s_mfma_kernel(const bf16_t* __restrict__ qkv, float* __restrict__ part,
+template <typename T>  // bf16_t or f16_t: the same fragments, v_mfma_f32_16x16x32_bf16 / _f16
+__global__ __launch_bounds__(256) void ce_t2s_mfma_kernel(const T* __restrict__ qkv, float* __restrict__ part,
                                                           const unsigned char* __restrict__ tmask, int Bm, int pitch,
                                                           int n_t, int k, int C, float scale) {
     __shared__ float red[2][4][16];
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(256) void ce_t2s_mfma_kernel(const bf16_t* __restri
         return;
     }
     const int qseq = gq < n_t ? b : b + Bm, qrow = gq < n_t ? gq : gq - n_t;
-    const bf16_t* qp = qkv + ((int64_t)qseq * pitch + qrow) * rs + h * 64 + 8 * lg;
+    const T* qp = qkv + ((int64_t)qseq * pitch + qrow) * rs + h * 64 + 8 * lg;
     const u32x4 q0 = *(const u32x4*)qp, q1 = *(const u32x4*)(qp + 32);
     u32x4 kf[CE_MAXI][2];
 #pragma unroll
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(256) void ce_t2s_mfma_kernel(const bf16_t* __restri
         if (kb < nkb) {
             const int key = min(kb * 16 + l16, nk - 1);  // clamped; masked below
             const int seq = key < k ? b : b + Bm, row = n_t + (key < k ? key : key - k);
-            const bf16_t* kp = qkv + ((int64_t)seq * pitch + row) * rs + C + h * 64 + 8 * lg;
+            const T* kp = qkv + ((int64_t)seq * pitch + row) * rs + C + h * 64 + 8 * lg;
             kf[i][0] = *(const u32x4*)kp;
             kf[i][1] = *(const u32x4*)(kp + 32);
         }
@@ -217,10 +224,8 @@ __global__ __launch_bounds__(256) void ce_t2s_mfma_kernel(const bf16_t* __restri
         const int kb = w + 4 * i;
         if (kb < nkb) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[i][0]),
-                                                          __builtin_bit_cast(bf16x8, q0), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[i][1]),
-                                                          __builtin_bit_cast(bf16x8, q1), acc, 0, 0, 0);
+            acc = mfma16x16x32<T>(kf[i][0], q0, acc);
+            acc = mfma16x16x32<T>(kf[i][1], q1, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 acc[r] = kb * 16 + 4 * lg + r < nk ? acc[r] * scale : -INFINITY;
@@ -399,6 +404,48 @@ __global__ __launch_bounds__(64 * CE_RG_ROWS) void ce_rows_gather_kernel(const f
     }
 }
 
+// The same row movement for the template-cached search pass, whose streams hold only the search rows
+// ([S][rows][C], no template rows in front): the fp32 rows and / or their copy in the GEMM operand type,
+// the 16-bit copy as one packed 8-byte store per float4 loaded.  The index rows are idx_pitch apart
+// (mmt_ce_select's order vector keeps the pitch of the unpruned sequence).
+template <typename TO>
+MMT_DEV void ce_store4(TO* p, float4 v);
+template <> MMT_DEV void ce_store4<float>(float* p, float4 v) { *(float4*)p = v; }
+template <> MMT_DEV void ce_store4<bf16_t>(bf16_t* p, float4 v) {
+    *(uint2*)p = make_uint2(pack2<bf16_t>(v.x, v.y), pack2<bf16_t>(v.z, v.w));
+}
+template <> MMT_DEV void ce_store4<f16_t>(f16_t* p, float4 v) {
+    *(uint2*)p = make_uint2(pack2<f16_t>(v.x, v.y), pack2<f16_t>(v.z, v.w));
+}
+template <typename TO>
+__global__ __launch_bounds__(64 * CE_RG_ROWS) void ce_rows_gather_cast_kernel(const float* __restrict__ src,
+                                                                              int src_rows, float* __restrict__ dst,
+                                                                              TO* __restrict__ dst_t, int dst_rows,
+                                                                              const int* __restrict__ idx,
+                                                                              int idx_pitch, int C4) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * CE_RG_ROWS + (threadIdx.x >> 6), s = blockIdx.y;
+    if (r >= dst_rows) return;
+    const int j = idx[(int64_t)s * idx_pitch + r];
+    const bool live = j >= 0 && j < src_rows;
+    const float4* sp = (const float4*)src + ((int64_t)s * src_rows + (live ? j : 0)) * C4;
+    const int64_t dro = ((int64_t)s * dst_rows + r) * C4;  // in float4 (4-element) units
+    float4 v[CE_RG_V];
+#pragma unroll
+    for (int i = 0; i < CE_RG_V; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live && c < C4) v[i] = sp[c];
+    }
+#pragma unroll
+    for (int i = 0; i < CE_RG_V; ++i) {
+        const int c = lane + 64 * i;
+        if (c < C4) {
+            if (dst) ((float4*)dst)[dro + c] = v[i];
+            if (dst_t) ce_store4<TO>(dst_t + 4 * (dro + c), v[i]);
+        }
+    }
+}
+
 // One workgroup per sequence: the inverse staged in LDS (n_out <= CE_MAXINV), filled with -1, then
 // slot j written at inv[idx_in[j]] (entries outside [0, n_out) skipped; distinct entries: one writer
 // per word, no atomics), then copied out whole.
@@ -426,10 +473,15 @@ extern "C" int mmt_ce_t2s_attention_masked(const void* qkv, float* partial, cons
         tok_pitch < n_t + n_s || n_s > CE_MAXK)
         return MMT_EBADARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMT_BF16) {
+    if (dtype == MMT_BF16 || dtype == MMT_F16) {
         if (2 * n_s > 4 * CE_MAXI * 16) return MMT_EBADARG;
-        hipLaunchKernelGGL(ce_t2s_mfma_kernel, dim3((unsigned)(2 * n_t / CE_QBM), (unsigned)H, (unsigned)Bm), dim3(256),
-                           0, st, (const bf16_t*)qkv, partial, template_mask, Bm, tok_pitch, n_t, n_s, C, scale);
+        const dim3 grid((unsigned)(2 * n_t / CE_QBM), (unsigned)H, (unsigned)Bm);
+        if (dtype == MMT_BF16)
+            hipLaunchKernelGGL(ce_t2s_mfma_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qkv, partial,
+                               template_mask, Bm, tok_pitch, n_t, n_s, C, scale);
+        else
+            hipLaunchKernelGGL(ce_t2s_mfma_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)qkv, partial,
+                               template_mask, Bm, tok_pitch, n_t, n_s, C, scale);
     } else if (dtype == MMT_F32) {
         const size_t shm = sizeof(float) * (CE_QB * 64 + CE_QB * (size_t)((2 * n_s + 3) & ~3));
         hipLaunchKernelGGL(ce_t2s_kernel<float>, dim3((unsigned)(2 * n_t / CE_QB), (unsigned)H, (unsigned)Bm),
@@ -467,6 +519,9 @@ extern "C" int mmt_ce_gather(const float* x, float* xc, void* xn, const int* ord
     if (!xn || xn_dtype == MMT_BF16)
         hipLaunchKernelGGL(ce_gather_kernel<bf16_t>, grid, dim3(256), 0, st, x, xc, (bf16_t*)xn, order, tok_pitch, n_t,
                            ns_full, C);
+    else if (xn_dtype == MMT_F16)
+        hipLaunchKernelGGL(ce_gather_kernel<f16_t>, grid, dim3(256), 0, st, x, xc, (f16_t*)xn, order, tok_pitch, n_t,
+                           ns_full, C);
     else if (xn_dtype == MMT_F32)
         hipLaunchKernelGGL(ce_gather_kernel<float>, grid, dim3(256), 0, st, x, xc, (float*)xn, order, tok_pitch, n_t,
                            ns_full, C);
@@ -484,6 +539,9 @@ extern "C" int mmt_ce_recover(const float* x, const int* gidx, int keep, void* o
     if (dtype == MMT_BF16)
         hipLaunchKernelGGL(ce_recover_kernel<bf16_t>, grid, dim3(256), 0, st, x, gidx, keep, (bf16_t*)out, tok_pitch, n_t,
                            ns_full, C);
+    else if (dtype == MMT_F16)
+        hipLaunchKernelGGL(ce_recover_kernel<f16_t>, grid, dim3(256), 0, st, x, gidx, keep, (f16_t*)out, tok_pitch, n_t,
+                           ns_full, C);
     else if (dtype == MMT_F32)
         hipLaunchKernelGGL(ce_recover_kernel<float>, grid, dim3(256), 0, st, x, gidx, keep, (float*)out, tok_pitch, n_t,
                            ns_full, C);
@@ -498,6 +556,28 @@ extern "C" int mmt_ce_rows_gather(const float* src, int src_rows, float* dst, in
         return MMT_EBADARG;
     hipLaunchKernelGGL(ce_rows_gather_kernel, dim3((unsigned)((dst_rows + CE_RG_ROWS - 1) / CE_RG_ROWS), (unsigned)S),
                        dim3(64 * CE_RG_ROWS), 0, (hipStream_t)stream, src, src_rows, dst, dst_rows, idx, C / 4);
+    return launch_status();
+}
+
+extern "C" int mmt_ce_rows_gather_cast(const float* src, int src_rows, float* dst, void* dst_t, int dst_rows,
+                                       const int* idx, int idx_pitch, int S, int C, int t_dtype, void* stream) {
+    if (idx_pitch == 0) idx_pitch = dst_rows;
+    if (!src || !idx || (!dst && !dst_t) || src == dst || (const void*)src == dst_t || (dst && (void*)dst == dst_t) ||
+        S <= 0 || S > 65535 || src_rows <= 0 || dst_rows <= 0 || idx_pitch < dst_rows || C <= 0 || C % 4 ||
+        C > 256 * CE_RG_V)
+        return MMT_EBADARG;
+    if (dst_t && t_dtype != MMT_BF16 && t_dtype != MMT_F16 && t_dtype != MMT_F32) return MMT_EBADARG;
+    const dim3 grid((unsigned)((dst_rows + CE_RG_ROWS - 1) / CE_RG_ROWS), (unsigned)S), block(64 * CE_RG_ROWS);
+    hipStream_t st = (hipStream_t)stream;
+    if (!dst_t || t_dtype == MMT_BF16)
+        hipLaunchKernelGGL(ce_rows_gather_cast_kernel<bf16_t>, grid, block, 0, st, src, src_rows, dst, (bf16_t*)dst_t,
+                           dst_rows, idx, idx_pitch, C / 4);
+    else if (t_dtype == MMT_F16)
+        hipLaunchKernelGGL(ce_rows_gather_cast_kernel<f16_t>, grid, block, 0, st, src, src_rows, dst, (f16_t*)dst_t,
+                           dst_rows, idx, idx_pitch, C / 4);
+    else
+        hipLaunchKernelGGL(ce_rows_gather_cast_kernel<float>, grid, block, 0, st, src, src_rows, dst, (float*)dst_t,
+                           dst_rows, idx, idx_pitch, C / 4);
     return launch_status();
 }
 

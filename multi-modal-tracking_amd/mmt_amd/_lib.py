@@ -138,6 +138,7 @@ _PROTOS = {
     "mmt_ce_recover": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp],
     "mmt_ce_rows_gather": [vp, i32, vp, i32, vp, i32, i32, vp],
     "mmt_ce_index_invert": [vp, i32, vp, i32, i32, vp],
+    "mmt_ce_rows_gather_cast": [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp],
     "mmt_sample_target": [ctypes.POINTER(CropParams), i32, vp],
     "mmt_track_update": [vp, vp, vp, i32, i32, i32, i32, f64, vp],
     "mmt_sample_target_table": [vp, vp, i32, i32, vp],

@@ -441,9 +441,6 @@ class MixFormer_RGBT_CE(MixFormer_RGBT_Shared):
         finally:
             self._mask = None
 
-    def set_online(self, template, online_template):
-        raise NotImplementedError("the template K/V cache is not defined for candidate elimination")
-
 
 class MixFormer_RGBT_OnlineScore(_HipTracker):
     """Asymmetric model + score prediction module (asymmetric_shared_online.py:337-413)."""

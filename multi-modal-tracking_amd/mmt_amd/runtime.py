@@ -85,8 +85,6 @@ class MixFormerRGBTRuntime:
             raise ValueError("unknown variant %r" % (variant,))
         if dtype not in (torch.bfloat16, torch.float16, torch.float32):
             raise ValueError("dtype must be torch.bfloat16, torch.float16 or torch.float32")
-        if dtype == torch.float16 and variant == "asym_ce":
-            raise NotImplementedError("candidate elimination runs in bf16 / fp32 (its selection kernels have no fp16 form)")
         if dtype == torch.bfloat16 and variant == "rgb":
             # the RGB-only MixFormer has no fusion (GroupNorm) between backbone and corner head: its score
             # maps carry the backbone's scale (logit std ~8.6 on the golden inputs, ~4 effective soft-argmax
@@ -331,9 +329,13 @@ class MixFormerRGBTRuntime:
                        "XS": e(B, C, t=f32), "Q1": e(B, C, t=f32), "KV1": e(B * d.n_t, 2 * C, t=f32),
                        "M1": e(B, C, t=f32), "M2": e(B, C, t=f32), "SC": e(B, 1, t=f32)})
         if self.ce:
-            nparts = d.H * (2 * d.n_t // 8)  # (bf16 uses 16-query blocks: half of it)
+            nparts = d.H * (2 * d.n_t // 8)  # (the 16-bit types use 16-query blocks: half of it)
+            # CEG[stage] [S][ns]: mmt_ce_select writes slots [0, keep) of a row and nothing ever writes the rest,
+            # which stays -1 as allocated: the cached search pass inverts whole rows (mmt_ce_index_invert skips
+            # entries outside [0, ns)).  CEI: that inverse.
             ws.update({"XC": e(R, C, t=f32), "CEP": e(B * nparts * 2 * ns, t=f32),
-                       "CEG": [e(S, ns, t=torch.int32) for _ in self.ce], "CEO": e(S, ns, t=torch.int32),
+                       "CEG": [torch.full((S, ns), -1, device=dev, dtype=torch.int32) for _ in self.ce],
+                       "CEO": e(S, ns, t=torch.int32), "CEI": e(S, ns, t=torch.int32),
                        "CEM": [e(B, 2 * ns, t=f32) for _ in self.ce],
                        "CEMASK": torch.ones(B, 2 * d.n_t, device=dev, dtype=torch.uint8)})
         ws["plan"] = self._build_plan(ws, False)
@@ -422,7 +424,17 @@ class MixFormerRGBTRuntime:
         every sequence back to back ([S][nr], modality groups of B sequences), so every GEMM reads and
         writes plain rows (the compact epilogues and the LayerNorm-statistics hand-off apply); only the
         qkv GEMM writes through an output row map into the [S][ntok] per-layer cache, and the attention
-        stores its part's rows compact (mmt_attn_params.out_pitch / out_q0)."""
+        stores its part's rows compact (mmt_attn_params.out_pitch / out_q0).
+        Candidate elimination (asym_ce) in the cached passes: the "t" pass is the asym plan (template queries
+        never see a search key, so pruning cannot reach them).  The "s" pass ranks the candidates at a CE layer
+        from that layer's cache buffer -- the template Q rows the "t" pass left there and the K rows of the k
+        search tokens this pass has just written -- and gathers the compact [S][k] streams into [S][keep]
+        (mmt_ce_rows_gather_cast).  From then on the part is keep rows per sequence: the qkv GEMM maps them to
+        cache rows [n_t, n_t + keep) and the attention runs on ntok = n_t + keep at pitch d.ntok.  Cache rows
+        [n_t + keep, d.ntok) of the later layers hold whatever an earlier frame left: the selection reads K rows
+        [n_t, n_t + k) and the attention keys [0, n_t + keep) only, both written before they are read, so
+        nothing reads a stale row (tests/test_gpu_ce_cache.py fills them with NaN).
+        Returns (fp32 stream of the output, stages run, (final gidx, its keep) or None)."""
         d, W, B = self.d, self.w, ws["B"]
         C, ntok = d.C, d.ntok
         S = d.nmod * B
@@ -441,7 +453,9 @@ class MixFormerRGBTRuntime:
 
         def qat(t, g=0):  # the same in the [S][ntok] qkv stream
             return P(t, (g * B * ntok + off) * 3 * C)
-        qmap = dict(cmap=(nr, ntok)) if compact else {}  # qkv rows of the part into the [S][ntok] cache
+
+        def qmap():  # qkv rows of the part (nr of them) into the [S][ntok] cache
+            return dict(cmap=(nr, ntok))
 
         def rmap(ld):  # after candidate elimination (full forward): the first nr rows of each pitch-ntok sequence
             if compact or nr == ntok:
@@ -481,9 +495,7 @@ class MixFormerRGBTRuntime:
                        M=S * nr, N=C, K=KP, lda=KP, ldc=C, bias=[P(W["bb"][0]["patch_b"])], r=[pos_at(0)], ldr=C,
                        r_mode=1, r_p0=nr, c_f32=1, **cp, **pseg)
         # --- transformer blocks
-        if self.ce and part is not None:
-            refuse_cache_with_ce(self.variant)
-        stage = 0
+        stage, final = 0, None
         for i in range(d.depth):
             gm = B * nr  # rows per modality group (nr shrinks after each elimination stage)
             QKV = ws["QKV"] if qkv_layers is None else qkv_layers[i]
@@ -508,18 +520,20 @@ class MixFormerRGBTRuntime:
             if fold:  # LayerNorm 1 folded into qkv: A = XN = bf16 copy of the residual stream X
                 self._gemm(plan, "qkv", a=rows2(XN, C), w=fl("attn.qkv.fw"), c=qrows2, M=gm, N=3 * C,
                            K=C, lda=C, ldc=3 * C, bias=fl("attn.qkv.fb"), ln_colsum=fl("attn.qkv.fcs"), ln_eps=1e-6,
-                           ln_stats_in=rows2(LNST, nst) if hand else None, **(qmap if compact else rmap(C)))
+                           ln_stats_in=rows2(LNST, nst) if hand else None, **(qmap() if compact else rmap(C)))
             else:
                 plan.append((LIB.mmt_layernorm, (P(X), None, 0, None, P(XN), P(n1[0][0]), P(n1[0][1]), P(n1[1][0]),
                                                  P(n1[1][1]), R, B * rp, C, 1e-6, cdt), "ln1", None))
                 self._gemm(plan, "qkv", a=rows(XN, C), w=wl("attn.qkv.w"), c=[qat(QKV, g) for g in range(len(rows(XN, C)))],
-                           M=Mg, N=3 * C, K=C, lda=C, ldc=3 * C, bias=wl("attn.qkv.b"), **(qmap if compact else rmap(C)))
+                           M=Mg, N=3 * C, K=C, lda=C, ldc=3 * C, bias=wl("attn.qkv.b"), **(qmap() if compact else rmap(C)))
             ap = AttnParams()
             ap.qkv, ap.out, ap.S, ap.Bm, ap.ntok, ap.n_t, ap.C, ap.H = P(QKV), P(AO), S, B, ntok, d.n_t, C, d.H
             if compact:  # the part's rows stored compact
                 ap.out_pitch, ap.out_q0 = nr, off
             if part is None and nr != ntok:  # after an elimination stage: first nr rows of each sequence
                 ap.ntok, ap.tok_pitch = nr, ntok
+            if part == "s" and nr != d.ns:  # the same in the cached search pass: nr search rows survive
+                ap.ntok, ap.tok_pitch = d.n_t + nr, ntok
             ap.asym = 1 if self.variant in ("asym", "asym_online", "asym_ce") else 0
             ap.scale = 1.0 / LOG2E if self.fold_ln else (C // d.H) ** -0.5  # see q_scale
             ap.q_part = {None: 0, "t": 1, "s": 2}[part]
@@ -530,11 +544,11 @@ class MixFormerRGBTRuntime:
                 cpx["ln_stats_out"] = rows(LNST, nst)
             self._gemm(plan, "proj", a=rows(AO, C), w=wl("attn.proj.w"), c=rows(X, C), M=Mg, N=C, K=C, lda=C,
                        ldc=C, bias=wl("attn.proj.b"), r=rows(X, C), ldr=C, c_f32=1, **cpx, **rmap(C))
-            if i in self.ce:  # candidate elimination after the attention residual, before the MLP
-                k = nr - d.n_t
+            if i in self.ce and part != "t":  # candidate elimination after the attention residual, before the MLP
+                k = nr if compact else nr - d.n_t  # search tokens left
                 keep = math.ceil(self.ce[i] * k)
                 if keep < k:
-                    nparts = d.H * (2 * d.n_t // (16 if cdt == MMT_BF16 else 8))  # mmt_ce_t2s_attention blocks
+                    nparts = d.H * (2 * d.n_t // (8 if cdt == MMT_F32 else 16))  # mmt_ce_t2s_attention blocks
                     masked = self.ce_mask_count is not None
                     plan.append((LIB.mmt_ce_t2s_attention_masked,
                                  (P(QKV), P(ws["CEP"]), P(ws["CEMASK"]) if masked else None, B, ntok, d.n_t, k, C, d.H,
@@ -545,11 +559,18 @@ class MixFormerRGBTRuntime:
                                                      P(ws["CEO"]), P(ws["CEM"][stage]),
                                                      1.0 / (d.H * nq)), "ce_select", None))
                     Xn = ws["XC"] if X is ws["X"] else ws["X"]
-                    plan.append((LIB.mmt_ce_gather, (P(X), P(Xn), P(XN) if fold else None, P(ws["CEO"]), S, ntok,
-                                                     d.n_t, keep, d.ns, C, cdt), "ce_gather", None))
+                    if compact:  # packed search rows [S][k] -> [S][keep] (+ the copy the folded GEMMs read)
+                        plan.append((LIB.mmt_ce_rows_gather_cast,
+                                     (P(X), k, P(Xn), P(XN) if fold else None, keep, P(ws["CEO"]), d.ns, S, C, cdt),
+                                     "ce_rows_gather_cast", None))
+                        nr = rp = keep
+                        R = S * rp
+                    else:
+                        plan.append((LIB.mmt_ce_gather, (P(X), P(Xn), P(XN) if fold else None, P(ws["CEO"]), S, ntok,
+                                                         d.n_t, keep, d.ns, C, cdt), "ce_gather", None))
+                        nr = d.n_t + keep
                     X = Xn
-                    nr = d.n_t + keep
-                    ws["CE_FINAL"] = (ws["CEG"][stage], keep)
+                    final = (ws["CEG"][stage], keep)
                     stage += 1
                     Mg = gm = B * nr
                     if not two:
@@ -565,7 +586,7 @@ class MixFormerRGBTRuntime:
                            K=C, lda=C, ldc=d.hidden, bias=wl("mlp.fc1.b"), act=1, **rmap(C))
             self._gemm(plan, "fc2", a=rows(HID, d.hidden), w=wl("mlp.fc2.w"), c=rows(X, C), M=Mg, N=C, K=d.hidden,
                        lda=d.hidden, ldc=C, bias=wl("mlp.fc2.b"), r=rows(X, C), ldr=C, c_f32=1, **cpx, **rmap(d.hidden))
-        return (X, stage)
+        return (X, stage, final)
 
     def _image_args(self, t, o, s):
         """mmt_patch_im2col's six image pointers (t0, t1, o0, o1, s0, s1); the RGB-only model passes
@@ -576,8 +597,9 @@ class MixFormerRGBTRuntime:
 
     def _plan_tail(self, plan, ws, score, xf=None, spm_kv1=True, compact=False):
         """Fusion, corner head (and score head) on the backbone output's search rows.  xf = (the fp32
-        stream holding the backbone output, elimination stages run) from _plan_backbone; compact: the
-        search pass of the template K/V cache, whose streams hold only the search rows ([S][ns])."""
+        stream holding the backbone output, elimination stages run, (final gidx, keep)) from _plan_backbone;
+        compact: the search pass of the template K/V cache, whose streams hold only the search rows ([S][ns],
+        or [S][keep] in xf's stream after candidate elimination)."""
         d, W, B = self.d, self.w, ws["B"]
         C, ns, dm = d.C, d.ns, d.d_model
         ntok = ns if compact else d.ntok  # rows per sequence of the backbone output
@@ -591,10 +613,17 @@ class MixFormerRGBTRuntime:
             # _recover_search (asymmetric_shared_ce.py:426-447): surviving rows back to their original
             # search positions, zeros where pruned, in the dtype the fusion reads
             XT = XN if fold else ws["XT"]
-            gf, kf = ws["CE_FINAL"]
-            plan.append((LIB.mmt_ce_recover, (P(xf[0]), P(gf), kf, P(XT), 2 * B, ntok, d.n_t, ns, C, cdt),
-                         "ce_recover", None))
-            ws["XOUT"] = XT
+            gf, kf = xf[2]  # of the backbone plan this tail follows (not shared through the workspace)
+            if compact:
+                # packed [S][kf] -> [S][ns]: one indexed row copy through the inverse of the final gidx (its
+                # rows are -1 past kf, see workspace), instead of a scan of gidx per output row
+                plan.append((LIB.mmt_ce_index_invert, (P(gf), ns, P(ws["CEI"]), ns, 2 * B), "ce_index_invert", None))
+                plan.append((LIB.mmt_ce_rows_gather_cast, (P(xf[0]), kf, None, P(XT), ns, P(ws["CEI"]), ns, 2 * B, C, cdt),
+                             "ce_recover_rows", None))
+            else:
+                plan.append((LIB.mmt_ce_recover, (P(xf[0]), P(gf), kf, P(XT), 2 * B, ntok, d.n_t, ns, C, cdt),
+                             "ce_recover", None))
+                ws["XOUT"] = XT
         elif fold:
             XT = XN  # the last fc2 already wrote the bf16 copy of the backbone output
         else:
@@ -780,13 +809,7 @@ class MixFormerRGBTRuntime:
         ws = self.workspace(B)
         score = bool(run_score_head) and self.variant == "asym_online"
         self.load_inputs(ws, template, online_template, search)
-        if (ce_template_mask is None) != (self.ce_mask_count is None):
-            raise ValueError("ce_template_mask must be given exactly when the runtime was built with ce_mask_count")
-        if ce_template_mask is not None:
-            m = ws["CEMASK"]
-            if tuple(ce_template_mask.shape) != tuple(m.shape):
-                raise ValueError("ce_template_mask shape %s, expected %s" % (tuple(ce_template_mask.shape), tuple(m.shape)))
-            m.copy_(ce_template_mask.to(device=m.device, dtype=torch.uint8), non_blocking=True)
+        self._load_ce_mask(ws, ce_template_mask)
         if use_graph:
             g = self._graphs.get((B, score))
             if g is None:
@@ -817,7 +840,10 @@ class MixFormerRGBTRuntime:
         pass ("plan_t") fills once per template update and whose search rows each frame's pass
         ("plan_s"; "plan_s_score" with the score head) fills before the layer's attention reads
         all of them.  Template queries attend template keys only, so template + search passes
-        reproduce the full forward (same kernels, same per-row arithmetic)."""
+        reproduce the full forward (same kernels, same per-row arithmetic).  With candidate elimination
+        the search pass prunes as the full forward does (_plan_backbone); the selection buffers (CEG, CEO,
+        CEM, CEMASK) are the workspace's, shared with the full-forward plan, which is built before and not
+        touched here."""
         ws = self.workspace(B, key)
         if "plan_t" not in ws:
             d = self.d
@@ -829,8 +855,8 @@ class MixFormerRGBTRuntime:
                 self._plan_spm_kv1(ws["plan_t"], ws, compact=True)
             for score in ((False, True) if self.variant == "asym_online" else (False,)):
                 plan = []
-                self._plan_backbone(plan, ws, "s", ws["QKVL"])
-                self._plan_tail(plan, ws, score, spm_kv1=False, compact=True)
+                xf = self._plan_backbone(plan, ws, "s", ws["QKVL"])
+                self._plan_tail(plan, ws, score, xf, spm_kv1=False, compact=True)
                 ws["plan_s_score" if score else "plan_s"] = plan
         return ws
 
@@ -846,9 +872,20 @@ class MixFormerRGBTRuntime:
             dst.copy_(src, non_blocking=True)
         self.run_plan(ws["plan_t"])
 
-    def forward_search(self, search, run_score_head=False):
+    def _load_ce_mask(self, ws, ce_template_mask):
+        """forward()'s ce_template_mask contract: given exactly when the runtime was built with
+        ce_mask_count, shape (B, 2 n_t); copied into the workspace before the plan runs."""
+        if (ce_template_mask is None) != (self.ce_mask_count is None):
+            raise ValueError("ce_template_mask must be given exactly when the runtime was built with ce_mask_count")
+        if ce_template_mask is not None:
+            m = ws["CEMASK"]
+            if tuple(ce_template_mask.shape) != tuple(m.shape):
+                raise ValueError("ce_template_mask shape %s, expected %s" % (tuple(ce_template_mask.shape), tuple(m.shape)))
+            m.copy_(ce_template_mask.to(device=m.device, dtype=torch.uint8), non_blocking=True)
+
+    def forward_search(self, search, run_score_head=False, ce_template_mask=None):
         """Search pass against the cached template (set_template first, same batch size): boxes
-        (B,4) cxcywh and scores as forward() returns them."""
+        (B,4) cxcywh and scores as forward() returns them.  ce_template_mask: as forward()'s."""
         B = search[0].shape[0]
         ws = self.cache_workspace(B)
         score = bool(run_score_head) and self.variant == "asym_online"
@@ -856,6 +893,7 @@ class MixFormerRGBTRuntime:
             if src.shape != dst.shape:
                 raise ValueError("input shape %s, expected %s" % (tuple(src.shape), tuple(dst.shape)))
             dst.copy_(src, non_blocking=True)
+        self._load_ce_mask(ws, ce_template_mask)
         self.run_plan(ws["plan_s_score"] if score else ws["plan_s"])
         return ws["BOX"], (ws["SC"].view(-1) if score else None)
 
@@ -878,8 +916,9 @@ class MixFormerRGBTRuntime:
         N, D = int(N), int(D)
         if N < 1 or not 1 <= D <= N:
             raise ValueError("slot cache needs 1 <= refresh capacity D <= N slots, got D=%d N=%d" % (D, N))
+        refuse_cache_with_ce(self.variant)  # before anything is allocated
         fresh = "plan_t" not in self._ws.get(N, ())
-        ws = self.cache_workspace(N)  # raises NotImplementedError for candidate elimination
+        ws = self.cache_workspace(N)
         if fresh:
             for q in ws["QKVL"]:
                 q.zero_()
@@ -1017,10 +1056,12 @@ class MixFormerRGBTRuntime:
 
 
 def refuse_cache_with_ce(variant):
-    """The template K/V cache (whole-batch or per slot) has no candidate-elimination form: the pruning reads
-    the template queries' attention over the search keys of the current frame."""
+    """The per-slot template K/V cache has no candidate-elimination form: the pruning reads the template
+    queries' attention over the search keys of the current frame, i.e. the template rows' Q, and the slot
+    refresh moves only their K and V columns into the N-slot cache.  (The whole-batch cache keeps whole rows
+    and prunes: _plan_backbone.)"""
     if variant == "asym_ce":
-        raise NotImplementedError("the template K/V cache is not defined for candidate elimination")
+        raise NotImplementedError("the per-slot template K/V cache is not defined for candidate elimination")
 
 
 def slot_chunks(slots, capacity):
