@@ -121,6 +121,61 @@ MMT_DEV uint2 gemm_tr16(const unsigned char* p) {
 // bit 3 distinct, land on 8 disjoint 32-B bank groups).
 MMT_DEV int gemm_trsw(int k) { return 2 * ((k & 3) | (((k >> 3) & 1) << 2)); }
 
+// ---- Lean frame kernels (gemm_glds_frame_kernel below): the four ViT GEMMs of the batch-1 frame are one round of
+// workgroups each, and about half of such a launch is fixed cost that grows with the code a workgroup walks through
+// cold and the kernel arguments it loads.  Their entry points take one of these argument blocks instead of
+// mmt_gemm_params: the members the path reads carry the public struct's names, so gemm_glds_tile runs on either type;
+// everything the frame fixes is a static constant of that name (no argument load, and the tests on it fold away), and
+// what is the same for the whole grid (tile counts, the XCD remap's split, 1 / K) comes from the host launcher.
+struct gemm_lean_null {  // a per-group pointer the path never has
+    MMT_DEV constexpr decltype(nullptr) operator[](int) const { return nullptr; }
+};
+struct gemm_lean_fixed {  // plain GEMM mode, identity row maps, no split-K
+    static constexpr int64_t a_seg_rows = INT32_MAX, a_segs_a = 1, a_stride_a = 0, a_stride_b = 0;
+    static constexpr int64_t c_seg_rows = 0, c_seg_pitch = 0;
+    static constexpr int32_t k_split = 0, conv_h = 0, conv_up = 1, conv_cin = 0, conv_k3 = 0;
+    static constexpr int32_t r_mode = 0, r_p0 = 1, r_p1 = 1, r_t = 0;
+    static constexpr float* sk_ws = nullptr;
+    static constexpr uint32_t* sk_cnt = nullptr;
+    static constexpr int64_t sk_cnt_n = 0;
+    gemm_lean_null a1;
+};
+struct gemm_lean_grid {  // host-computed, the same for every workgroup
+    int32_t per_g;       // tiles per group
+    int32_t tn_magic;    // tile / tiles_m == (tile * tn_magic) >> 16 for every tile of the grid
+    int32_t q8, r8;      // workgroups / 8 and % 8 (XCD remap)
+    float inv_k;         // 1 / K
+};
+template <int EPI, int ACT>
+struct gemm_lean_args;
+// EPI 1: 16-bit C = act(LayerNorm fold on handed-in statistics + bias)  (qkv, fc1)
+template <int ACT>
+struct gemm_lean_args<1, ACT> : gemm_lean_fixed, gemm_lean_grid {
+    const void *a[2], *w[2];
+    const float *bias[2], *ln_colsum[2], *ln_stats_in[2];
+    void* c[2];
+    int32_t M, N, K, lda, ldc;
+    float ln_eps;
+    static constexpr int32_t act = ACT, c2_copy = 0, ldr = 0;
+    gemm_lean_null r, c2, ln_stats_out;
+};
+// EPI 2: fp32 C = acc + bias + R, C2 its 16-bit copy, the next LayerNorm's row statistics  (proj, fc2)
+template <int ACT>
+struct gemm_lean_args<2, ACT> : gemm_lean_fixed, gemm_lean_grid {
+    const void *a[2], *w[2];
+    const float *bias[2], *r[2];
+    void *c[2], *c2[2];
+    float* ln_stats_out[2];
+    int32_t M, N, K, lda, ldc, ldr;
+    static constexpr int32_t act = 0, c2_copy = 1;
+    static constexpr float ln_eps = 0.f;
+    gemm_lean_null ln_colsum, ln_stats_in;
+};
+template <typename P>
+struct gemm_is_lean { static constexpr bool value = false; };
+template <int EPI, int ACT>
+struct gemm_is_lean<gemm_lean_args<EPI, ACT>> { static constexpr bool value = true; };
+
 // WGM x WGN waves per k-group own WM x WN sub-tiles; KS k-groups split the K-steps.  CONV: A is
 // the implicit im2col of an NHWC 3x3/pad-1 (conv_k3) or 1x1 convolution, input read through the
 // nearest-upsample index map (gemm.hip's conv mode).  LNF: LayerNorm folded into the GEMM
@@ -134,8 +189,8 @@ MMT_DEV int gemm_trsw(int k) { return 2 * ((k & 3) | (((k >> 3) & 1) << 2)); }
 // EPI 2: the compact epilogue of the residual producers (fp32 C = acc + bias + R, its 16-bit copy C2, the next
 // LayerNorm's row statistics).
 template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, bool CONV, int LNM, int OCC = 1, bool RS = false,
-          int EPI = 0>
-MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int tile, const int slice, const int nsk,
+          int EPI = 0, typename P = mmt_gemm_params>
+MMT_DEV void gemm_glds_tile(const P& p, const int g, const int tile, const int slice, const int nsk,
                             const int ntiles) {
     constexpr int NW = WGM * WGN, TPG = 64 * NW;  // waves / threads per k-group
     constexpr int KT = 64;                        // bf16 elements of K per step: 128-B rows
@@ -156,6 +211,9 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
     static_assert(!TB || (BM == 128 && BN == 128 && !CONV), "MN-major operands: 128x128 tiles");
     static_assert(KS == 1 || BM * BN * 4 <= KS * ST * STAGE, "k-group reduction buffer");
     // impl 9: its half-tile fp32 image (128 x 260 floats) and the row statistics exceed the 128 KiB ring
+    constexpr bool LEAN = gemm_is_lean<P>::value;  // a lean frame kernel's argument block
+    static_assert(!LEAN || (OCC == 1 && !CONV && !RS && (LNM == 0 || LNM == 2) && BM * BN <= 128 * 128 &&
+                            ((EPI == 1 && LNM == 2) || (EPI == 2 && LNM == 0))), "lean frame kernels");
     constexpr int LDS_BYTES = W4 ? (BM / 2) * (BN + 4) * 4 + BM * 8 + 64 : KS * ST * STAGE;
     static_assert(LDS_BYTES >= KS * ST * STAGE && LDS_BYTES <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
@@ -180,6 +238,9 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
         const int gsz = min(tiles_m - first, GM), r = tile - grp * GM * tiles_n;
         tm = first + r % gsz;
         tn = r / gsz;
+    } else if constexpr (LEAN) {  // the same order, the division by the host's multiplier
+        tn = (int)(((uint32_t)tile * (uint32_t)p.tn_magic) >> 16);
+        tm = tile - tn * tiles_m;
     } else {
         tm = tile % tiles_m;
         tn = tile / tiles_m;
@@ -238,7 +299,7 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
 
     auto issue = [&](int s) {  // this k-group's step s -> ring slot s % ST
         const int k = (min(s * KS + kg, nk - 1) + kb0) * KT + pch * 8;  // this lane's 8-element chunk
-        const bool kin = k < K;
+        const bool kin = LEAN || k < K;  // (lean: K % 64 == 0, no tail)
         unsigned char* base = ring + (s % ST) * STAGE;
         // MN-major images: lane -> row (lane >> 4) of its 4-row piece, physical chunk lane & 15
         const int kst = (min(s * KS + kg, nk - 1) + kb0) * KT, trq = lane >> 4, trc = lane & 15;
@@ -651,6 +712,7 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
         }
     };
     f32x4 rpa[RPRE ? NPASS0 : 1], rpb[RPRE ? NPASS0 : 1];
+    if constexpr (LEAN && EPI == 2) __builtin_assume(p.r[g] != nullptr);  // (the launcher checks)
     const bool rpre = RPRE && p.r[g] != nullptr && nsk == 1;  // wave-uniform
     if constexpr (RPRE) {
         if (rpre) {
@@ -869,6 +931,14 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
         }
     }
 #endif
+    if constexpr (LEAN) {  // present in every lean launch (the launcher checks)
+        __builtin_assume(bias != nullptr);
+        if constexpr (EPI == 2) {
+            __builtin_assume(R != nullptr);
+            __builtin_assume(C2 != nullptr);
+            __builtin_assume(p.ln_stats_out[g] != nullptr);
+        }
+    }
     const int n = n0 + tc, nc = min(n, N - 8);
     const bool csplit = p.c2_copy == 3 || p.c2_copy == 4;
     float* stats_out = p.c2_copy && !csplit && C2 ? p.ln_stats_out[g] : nullptr;
@@ -887,7 +957,9 @@ MMT_DEV void gemm_glds_tile(const mmt_gemm_params& p, const int g, const int til
         cs0 = *(const f32x4*)(p.ln_colsum[g] + nc);
         cs1 = *(const f32x4*)(p.ln_colsum[g] + nc + 4);
     }
-    const float inv_k = 1.f / (float)K;
+    float inv_k;
+    if constexpr (LEAN) inv_k = p.inv_k;  // the same IEEE quotient, from the host
+    else inv_k = 1.f / (float)K;
     // output row map (template K/V cache: search rows of a [S][ntok] stream); identity if c_seg_rows == 0
     // (32-bit unsigned division: M and the segment rows are < 2^31; a 64-bit one is a long software sequence)
     const int64_t csr = p.c_seg_rows > 0 ? p.c_seg_rows : INT64_MAX, csp = p.c_seg_pitch;
@@ -1153,6 +1225,20 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS)
     gemm_glds_tile<T, BM, BN, WGM, WGN, KS, ST, CONV, LNM, 1, false, EPI>(p, g, tile, slice, nsk, gridDim.x);
 }
 
+// Lean frame kernel: one tile shape, one K-loop form and one epilogue per entry point, a 1-D grid of one round
+// (<= 256 workgroups, <= 2 groups, no split-K) in the linear order of gemm_glds_kernel's (tiles, 1, groups) grid, so
+// the XCD placement, the tile a workgroup computes and every sum's order are those of gemm_glds_kernel at the same
+// tile shape: the outputs are bit-identical to it (tests/test_gpu_gemm_frame_kernels.py; impl 10 forces that kernel).
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT>
+__global__ __launch_bounds__(64 * WGM * WGN * KS)
+    __attribute__((amdgpu_waves_per_eu(WGM * WGN * KS / 4, WGM * WGN * KS / 4))) void gemm_glds_frame_kernel(
+        const gemm_lean_args<EPI, ACT> p) {
+    const int orig = blockIdx.x, xcd = orig & 7;
+    const int lin = xcd * p.q8 + min(xcd, p.r8) + (orig >> 3);  // gemm_xcd_lin
+    const int g = lin >= p.per_g ? 1 : 0;
+    gemm_glds_tile<T, BM, BN, WGM, WGN, KS, ST, false, LNM, 1, false, EPI>(p, g, lin - g * p.per_g, 0, 1, p.per_g);
+}
+
 // The same tile at two workgroups per CU (impl 8: 128x128, 8 waves, 2-slot ring = 64 KiB of LDS, <= 128
 // VGPRs): one workgroup's prologue / epilogue runs beside the other's K loop on the CU, which the one-
 // workgroup-per-CU tiles cannot overlap (large-M grids of short K: the training step's K = 768 GEMMs).
@@ -1339,12 +1425,71 @@ int64_t tiles_of(const mmt_gemm_params& p, int bm, int bn) {
     return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
 }
 
+
+// The tile shape (impl 1 / 3) of the lean frame kernel that covers p, 0 if none does: what the batch-1 frame plan
+// launches for qkv / fc1 (LayerNorm fold on handed-in statistics, compact 16-bit epilogue, 128x128) and proj / fc2
+// (compact residual producer with the 16-bit copy and the statistics hand-off, 64x64 with two k-groups) -- plain
+// rows, K % 64 == 0, <= 2 groups, one round of workgroups.  (glds_takes has checked alignment and the hand-off.)
+int lean_cfg(const mmt_gemm_params& p) {
+    if (p.groups > 2 || p.K % 64 || p.conv_h > 0 || p.k_split || p.a_seg_rows < p.M || p.c_seg_rows || p.a_t || p.w_t ||
+        p.row_scale || p.splitk >= 2 || std::max({p.lda, p.ldc, p.ldr}) > INT32_MAX)  // (a forced K split is honoured)
+        return 0;
+    for (int g = 0; g < p.groups; ++g)
+        if (!p.bias[g]) return 0;
+    int cfg = 0;
+    if (p.ln_fold == 2 && p.c2_copy == 0 && p.act <= 1 && compact_epilogue(p)) {
+        cfg = 1;
+    } else if (p.ln_fold == 0 && residual_epilogue(p)) {
+        for (int g = 0; g < p.groups; ++g)
+            if (!p.r[g] || !p.c2[g] || !p.ln_stats_out[g]) return 0;
+        cfg = 3;
+    } else {
+        return 0;
+    }
+    return tiles_of(p, kCands[cfg - 1].bm, kCands[cfg - 1].bn) * p.groups <= 256 ? cfg : 0;
+}
+
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT>
+void launch_lean(const mmt_gemm_params& p, hipStream_t st) {
+    gemm_lean_args<EPI, ACT> a{};
+    const int tiles_m = (p.M + BM - 1) / BM, nwg = (int)tiles_of(p, BM, BN) * p.groups;
+    a.per_g = nwg / p.groups;
+    a.tn_magic = 65536 / tiles_m + 1;  // exact while tile * tiles_m < 65536 (tile < 256, tiles_m <= 256)
+    a.q8 = nwg >> 3;
+    a.r8 = nwg & 7;
+    a.inv_k = 1.f / (float)p.K;
+    for (int g = 0; g < p.groups; ++g) {
+        a.a[g] = p.a[g];
+        a.w[g] = p.w[g];
+        a.bias[g] = p.bias[g];
+        a.c[g] = p.c[g];
+        if constexpr (EPI == 1) {
+            a.ln_colsum[g] = p.ln_colsum[g];
+            a.ln_stats_in[g] = p.ln_stats_in[g];
+        } else {
+            a.r[g] = p.r[g];
+            a.c2[g] = p.c2[g];
+            a.ln_stats_out[g] = p.ln_stats_out[g];
+        }
+    }
+    a.M = p.M, a.N = p.N, a.K = p.K, a.lda = (int32_t)p.lda, a.ldc = (int32_t)p.ldc;
+    if constexpr (EPI == 1) a.ln_eps = p.ln_eps;
+    else a.ldr = (int32_t)p.ldr;
+    hipLaunchKernelGGL((gemm_glds_frame_kernel<T, BM, BN, WGM, WGN, KS, ST, LNM, EPI, ACT>), dim3(nwg),
+                       dim3(64 * WGM * WGN * KS), 0, st, a);
+}
+
 }  // namespace
 
 // Returns 1 when the shape / layout is not one this kernel takes (caller uses gemm.hip's kernel).
 template <typename T>
 int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
     if (force < 0 || !glds_takes(p)) return 1;
+    // impl 10: gemm_glds_kernel where a lean frame kernel would run, at that kernel's tile shape and unsplit (A/B and
+    // the bitwise test of the lean kernels); every other parameter set as impl 0
+    const int lcfg = lean_cfg(p);
+    const bool no_lean = force == 10;
+    if (force == 10) force = lcfg;
     const int nk = (p.K + 63) / 64;
     const Cand* cands = kCands;
     // largest split the workspace allows for a candidate (each slice keeps >= ks K-steps)
@@ -1457,7 +1602,9 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
         nsk = 1;  // impl 8: no split-K
     } else if (cfg >= 1 && cfg <= 7) {
         const Cand& c = cands[cfg - 1];
-        if (p.splitk >= 2) {
+        if (no_lean) {
+            nsk = 1;
+        } else if (p.splitk >= 2) {
             nsk = std::min(p.splitk, max_split(c));
         } else if (p.splitk == 0) {
             float best = 1e30f;
@@ -1466,6 +1613,12 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
                 if (t < best) best = t, nsk = n;
             }
         }
+    }
+    if (!no_lean && nsk == 1 && cfg != 0 && cfg == lcfg) {  // the tile shapes of cases 1 / 3 below
+        if (cfg == 3) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0>(p, st);
+        else if (p.act == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 1>(p, st);
+        else launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 0>(p, st);
+        return 0;
     }
     switch (cfg) {
         case 1: launch<T, 128, 128, 2, 4, 1, 4>(p, nsk, st); break;

@@ -24,6 +24,12 @@ from mmt_amd import _lib as L  # noqa: E402
 SHAPES = [("qkv", 2, 528, 2304, 768, 0, 0), ("proj", 2, 528, 768, 768, 0, 1), ("fc1", 2, 528, 3072, 768, 1, 0),
           ("fc2", 2, 528, 768, 3072, 0, 1), ("qkv_ln", 2, 528, 2304, 768, 0, 0), ("fc1_ln", 2, 528, 3072, 768, 1, 0),
           ("qkv_ln2", 2, 528, 2304, 768, 0, 0), ("fc1_ln2", 2, 528, 3072, 768, 1, 0)]
+if os.environ.get("GEMM_STAMP_SHAPES") == "frame":
+    # the four launches of a ViT block as the batch-1 frame plan makes them: qkv / fc1 with handed-in LayerNorm
+    # statistics, proj / fc2 (_f) with the 16-bit copy and the statistics out.  GEMM_STAMP_IMPLS=0,10 gives the lean
+    # frame kernels (0) beside the general kernel at the same tile shape (10)
+    SHAPES = [("qkv_ln2", 2, 528, 2304, 768, 0, 0), ("proj_f", 2, 528, 768, 768, 0, 1), ("fc1_ln2", 2, 528, 3072, 768, 1, 0),
+              ("fc2_f", 2, 528, 768, 3072, 0, 1)]
 if os.environ.get("GEMM_STAMP_SHAPES") == "train":  # the training step's forward GEMMs (16 pairs: 8448 rows per backbone)
     SHAPES = [("t_qkv", 1, 8448, 2304, 768, 0, 0), ("t_fc1", 1, 8448, 3072, 768, 1, 0), ("t_proj", 1, 8448, 768, 768, 0, 1),
               ("t_fc2", 1, 8448, 768, 3072, 0, 1)]
@@ -42,6 +48,8 @@ def main():
         b = torch.randn(G, N, device="cuda")
         R = torch.randn(G, M, N, device="cuda")
         C = torch.empty(G, M, N, device="cuda", dtype=torch.float32 if res else torch.bfloat16)
+        C2 = torch.empty(G, M, N, device="cuda", dtype=torch.bfloat16)
+        ST = torch.empty(G, M, 2 * (N // 64), device="cuda")
         for impl in IMPLS:
             p = L.GemmParams()
             for g in range(G):
@@ -50,20 +58,24 @@ def main():
             p.lda, p.ldc, p.ldr = K, N, N
             p.a_seg_rows, p.a_segs_a = M, 1
             p.M, p.N, p.K, p.act, p.c_f32, p.groups, p.impl = M, N, K, act, 1 if res else 0, G, impl
+            if name.endswith("_f"):
+                p.c2_copy = 1
+                for g in range(G):
+                    p.c2[g], p.ln_stats_out[g] = C2[g].data_ptr(), ST[g].data_ptr()
             if "_ln" in name:  # _ln: statistics in the K loop; _ln2: handed in (ln_stats_in)
                 p.ln_fold, p.ln_eps = (2 if name.endswith("_ln2") else 1), 1e-6
                 stats = torch.ones(G, M, 2 * (K // 64), device="cuda")
                 for g in range(G):
                     p.ln_colsum[g] = b[g].data_ptr()
                     p.ln_stats_in[g] = stats[g].data_ptr()
-            if impl == 0:  # the library's choice, split-K allowed (as the frame's plan entries)
+            if impl in (0, 10):  # the library's choice, split-K allowed (as the frame's plan entries)
                 p.splitk, p.sk_ws, p.sk_ws_floats = 0, SK_WS[0].data_ptr(), SK_WS[0].numel()
                 p.sk_cnt, p.sk_cnt_n = SK_WS[1].data_ptr(), SK_WS[1].numel()
             s = torch.cuda.current_stream().cuda_stream
             for _ in range(10):
                 L.check(L.LIB.mmt_gemm(ctypes.byref(p), L.MMT_BF16, s), name)
             torch.cuda.synchronize()
-            if impl == 0:  # grid unknown here: the rows the last launch wrote (ended within 30 us of the last end)
+            if impl in (0, 10):  # grid unknown here: the rows the last launch wrote (ended within 30 us of the last end)
                 buf = (ctypes.c_ulonglong * (4096 * 8))()
                 L.check(L.LIB.mmt_gemm_stamps(buf, 4096 * 8), "stamps")
                 st = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.int64)
