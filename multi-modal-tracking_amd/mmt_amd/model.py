@@ -15,9 +15,10 @@ called.  The forward is the fixed HIP launch plan; the first call after construc
 `refresh_kernels()` after editing parameters in place).  There is no PyTorch fallback: without a
 HIP device and libmmt_hip.so the forward raises.
 
-Scope: inference (eval) of the hot path.  Fusion class Attention_Fusion_Bimodal_LNSpecific and
-head CORNER_UP only; the reference's other fusion/head classes are ablations
-out of scope.  Deviation D1: the fusion width follows MODEL.HIDDEN_DIM instead of the reference's
+Scope: inference (eval) of the hot path.  The deformable fusion front-ends (FUSION_CLASSES:
+Attention_Fusion_Bimodal, _LNSpecific, _LNSpecific_Sum, _LNSpecific_2, all run as the LNSpecific plan
+with weights tied) and head CORNER_UP only; the reference's other fusion/head
+classes are ablations out of scope.  Deviation D1: the fusion width follows MODEL.HIDDEN_DIM instead of the reference's
 hard-coded 768, so ViT-L (HIDDEN_DIM 1024) builds; for ViT-B both are 768.
 """
 import math
@@ -103,33 +104,53 @@ class MSDeformAttn_Bimodal(nn.Module):
 
 
 class DeformableTransformerEncoderLayer(nn.Module):
-    """deformable_encoder_lnspecific.py:111-160 parameters."""
+    """deformable_encoder_lnspecific.py:111-160 parameters (per-modality norm*_v / norm*_i);
+    ln_specific=False: deformable_encoder.py:111-137, one norm1 / norm2 for both modalities."""
 
-    def __init__(self, d_model, d_ffn):
+    def __init__(self, d_model, d_ffn, ln_specific=True):
         super().__init__()
         self.self_attn = MSDeformAttn_Bimodal(d_model)
         self.dropout1 = nn.Dropout(0.1)
-        self.norm1_v, self.norm1_i = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+        if ln_specific:
+            self.norm1_v, self.norm1_i = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+        else:
+            self.norm1 = nn.LayerNorm(d_model)
         self.linear1 = nn.Linear(d_model, d_ffn)
         self.dropout2 = nn.Dropout(0.1)
         self.linear2 = nn.Linear(d_ffn, d_model)
         self.dropout3 = nn.Dropout(0.1)
-        self.norm2_v, self.norm2_i = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+        if ln_specific:
+            self.norm2_v, self.norm2_i = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+        else:
+            self.norm2 = nn.LayerNorm(d_model)
 
 
 class DeformableTransformerEncoder(nn.Module):
-    def __init__(self, d_model, d_ffn, num_layers):
+    def __init__(self, d_model, d_ffn, num_layers, ln_specific=True):
         super().__init__()
-        self.layers = nn.ModuleList([DeformableTransformerEncoderLayer(d_model, d_ffn) for _ in range(num_layers)])
+        self.layers = nn.ModuleList([DeformableTransformerEncoderLayer(d_model, d_ffn, ln_specific)
+                                     for _ in range(num_layers)])
         self.num_layers = num_layers
 
 
 class DeformableAttentionFusion_LNSpecific(nn.Module):
+    ln_specific = True
+
     def __init__(self, d_model=512, num_encoder_layers=2, num_feature_levels=2):
         super().__init__()
         self.d_model, self.nhead = d_model, 8
-        self.encoder = DeformableTransformerEncoder(d_model, 4 * d_model, num_encoder_layers)
+        self.encoder = DeformableTransformerEncoder(d_model, 4 * d_model, num_encoder_layers, self.ln_specific)
         self.level_embed = nn.Parameter(torch.zeros(num_feature_levels, d_model))
+
+
+class DeformableAttentionFusion(DeformableAttentionFusion_LNSpecific):
+    """deformable_encoder.py:23-50 parameters: the same encoder with one norm1 / norm2 per layer."""
+
+    ln_specific = False
+
+
+def _adjust(cin, cout):
+    return nn.Sequential(nn.Conv2d(cin, cout, 1), nn.GroupNorm(32, cout))
 
 
 class Attention_Fusion_Bimodal_LNSpecific(nn.Module):
@@ -137,10 +158,68 @@ class Attention_Fusion_Bimodal_LNSpecific(nn.Module):
 
     def __init__(self, channels_num, d_model=512, num_feature_levels=2, num_encoder_layers=2):
         super().__init__()
-        self.adjust_v = nn.Sequential(nn.Conv2d(channels_num, d_model, 1), nn.GroupNorm(32, d_model))
-        self.adjust_i = nn.Sequential(nn.Conv2d(channels_num, d_model, 1), nn.GroupNorm(32, d_model))
+        self.adjust_v = _adjust(channels_num, d_model)
+        self.adjust_i = _adjust(channels_num, d_model)
         self.fusion_attention = DeformableAttentionFusion_LNSpecific(d_model, num_encoder_layers, num_feature_levels)
-        self.adjust_cat = nn.Sequential(nn.Conv2d(2 * d_model, channels_num, 1), nn.GroupNorm(32, channels_num))
+        self.adjust_cat = _adjust(2 * d_model, channels_num)
+
+
+class Attention_Fusion_Bimodal(nn.Module):
+    """fusion_utils.py:165-190 parameters: the LNSpecific front-end on the plain encoder (norm1 / norm2 serve
+    both modalities)."""
+
+    def __init__(self, channels_num, d_model=512, num_feature_levels=2, num_encoder_layers=6):
+        super().__init__()
+        self.adjust_v = _adjust(channels_num, d_model)
+        self.adjust_i = _adjust(channels_num, d_model)
+        self.fusion_attention = DeformableAttentionFusion(d_model, num_encoder_layers, num_feature_levels)
+        self.adjust_cat = _adjust(2 * d_model, channels_num)
+
+
+class Attention_Fusion_Bimodal_LNSpecific_Sum(nn.Module):
+    """fusion_utils.py:282-307 parameters: adjust_sum reads out_v + out_i (d_model channels)."""
+
+    def __init__(self, channels_num, d_model=512, num_feature_levels=2, num_encoder_layers=6):
+        super().__init__()
+        self.adjust_v = _adjust(channels_num, d_model)
+        self.adjust_i = _adjust(channels_num, d_model)
+        self.fusion_attention = DeformableAttentionFusion_LNSpecific(d_model, num_encoder_layers, num_feature_levels)
+        self.adjust_sum = _adjust(d_model, channels_num)
+
+
+class Attention_Fusion_Bimodal_LNSpecific_2(nn.Module):
+    """fusion_utils.py:321-342 parameters: adjust_in serves both modalities, adjust_out reads out_v + out_i."""
+
+    def __init__(self, channels_num, d_model=512, num_feature_levels=2, num_encoder_layers=6):
+        super().__init__()
+        self.adjust_in = _adjust(channels_num, d_model)
+        self.fusion_attention = DeformableAttentionFusion_LNSpecific(d_model, num_encoder_layers, num_feature_levels)
+        self.adjust_out = _adjust(d_model, channels_num)
+
+
+# MODEL.FUSION_CLASS values the builders accept: the deformable front-ends, each of which is the LNSpecific
+# one with some weights tied (fusion_parts below; DESIGN.md §4)
+FUSION_CLASSES = {c.__name__: c for c in (Attention_Fusion_Bimodal, Attention_Fusion_Bimodal_LNSpecific,
+                                          Attention_Fusion_Bimodal_LNSpecific_Sum, Attention_Fusion_Bimodal_LNSpecific_2)}
+
+
+def fusion_parts(fu):
+    """(adjust of RGB, adjust of TIR, tail, summed) of any front-end: the two input (conv, GroupNorm) pairs
+    (the same module twice where one serves both modalities), the output pair, and whether the output conv
+    reads out_v + out_i (d_model input channels) instead of their channel concat."""
+    if hasattr(fu, "adjust_in"):
+        return fu.adjust_in, fu.adjust_in, fu.adjust_out, True
+    if hasattr(fu, "adjust_sum"):
+        return fu.adjust_v, fu.adjust_i, fu.adjust_sum, True
+    return fu.adjust_v, fu.adjust_i, fu.adjust_cat, False
+
+
+def layer_norms(layer):
+    """((norm1 of RGB, norm1 of TIR), (norm2 of RGB, norm2 of TIR)) of an encoder layer or a ViT block:
+    the same module twice where one norm serves both modalities."""
+    if hasattr(layer, "norm1"):
+        return (layer.norm1, layer.norm1), (layer.norm2, layer.norm2)
+    return (layer.norm1_v, layer.norm1_i), (layer.norm2_v, layer.norm2_i)
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -363,6 +442,14 @@ class MixFormer_RGBT_Shared(_HipTracker):
         self.box_head = box_head
 
 
+class MixFormer_RGBT_Uni(MixFormer_RGBT_Shared):
+    """One plain ViT over both modalities stacked on the batch (mixformer_unibackbone.py:354-394): the shared
+    model whose blocks have one norm1 / norm2 for both modalities.  set_online / forward_test are the shared
+    model's (the reference's own address backbone_v / backbone_i, which this model lacks: defect D2)."""
+
+    variant = "uni"
+
+
 class MixFormer_RGBT_Asymmetric(MixFormer_RGBT_Shared):
     """Cross-modal asymmetric MAM (asymmetric_shared.py:336-368)."""
 
@@ -527,9 +614,9 @@ def _vit_spec(cfg):
 
 
 def _check_cfg(cfg):
-    if cfg.MODEL.FUSION_CLASS != "Attention_Fusion_Bimodal_LNSpecific":
-        raise NotImplementedError("FUSION_CLASS %r: only Attention_Fusion_Bimodal_LNSpecific (the hot path) is "
-                                  "implemented on MI355X" % cfg.MODEL.FUSION_CLASS)
+    if cfg.MODEL.FUSION_CLASS not in FUSION_CLASSES:
+        raise NotImplementedError("FUSION_CLASS %r: only the deformable front-ends %s are implemented on MI355X"
+                                  % (cfg.MODEL.FUSION_CLASS, ", ".join(sorted(FUSION_CLASSES))))
     if cfg.MODEL.HEAD_TYPE != "CORNER_UP":
         raise NotImplementedError("HEAD_TYPE %r: only CORNER_UP is implemented on MI355X" % cfg.MODEL.HEAD_TYPE)
 
@@ -547,7 +634,7 @@ def _head(cfg):
 
 
 def _fusion(cfg):
-    return Attention_Fusion_Bimodal_LNSpecific(cfg.MODEL.HIDDEN_DIM, 512, 2, cfg.MODEL.FUSION_LAYERS)
+    return FUSION_CLASSES[cfg.MODEL.FUSION_CLASS](cfg.MODEL.HIDDEN_DIM, 512, 2, cfg.MODEL.FUSION_LAYERS)
 
 
 def _load_checkpoint(path, key):
@@ -617,6 +704,22 @@ def build_mixformer_vit_rgbt_shared(cfg, train=True):
     return model
 
 
+def build_mixformer_vit_rgbt_uni(cfg, train=True):
+    """build_mixformer_vit_rgbt_uni (mixformer_unibackbone.py:434-464): the MAE weights load into the plain
+    blocks as they are; RGBT_PRETRAINED_PATH is a checkpoint of this same model minus the fixed tables
+    (:448-457)."""
+    _check_cfg(cfg)
+    bb = _backbone(cfg, False)
+    if train:
+        _load_mae(bb, cfg, False)
+    model = MixFormer_RGBT_Uni(bb, _head(cfg), _fusion(cfg), cfg.MODEL.HEAD_TYPE)
+    path = getattr(cfg.MODEL, "RGBT_PRETRAINED_PATH", "")
+    if train and path:
+        model.load_state_dict({k: v for k, v in _load_checkpoint(path, "net").items()
+                               if "pos_embed" not in k and "mask_token" not in k}, strict=False)
+    return model
+
+
 def build_asymmetric_shared(cfg, train=True):
     _check_cfg(cfg)
     bb = _backbone(cfg, True)
@@ -676,18 +779,19 @@ def build_mixformer_vit(cfg, train=True):
 
 BUILDERS = {"rgbt": build_mixformer_vit_rgbt, "shared": build_mixformer_vit_rgbt_shared,
             "asym": build_asymmetric_shared, "asym_online": build_asymmetric_shared_online_score,
-            "asym_ce": build_asymmetric_shared_ce, "rgb": build_mixformer_vit}
+            "asym_ce": build_asymmetric_shared_ce, "rgb": build_mixformer_vit, "uni": build_mixformer_vit_rgbt_uni}
 
 
-def hot_path_cfg(vit="base_patch16", search=320, template=128, fusion_layers=2, hidden=None):
+def hot_path_cfg(vit="base_patch16", search=320, template=128, fusion_layers=2, hidden=None,
+                 fusion_class="Attention_Fusion_Bimodal_LNSpecific"):
     """Config of BASELINE.json configs 2-5 (experiments/mixformer_vit_rgbt/attention_lasher_newfusion_2layer.yaml
-    with the search size overridden)."""
+    with the search size overridden); fusion_class: another of FUSION_CLASSES."""
     from .config import default_cfg
     cfg = default_cfg("asymmetric_shared_online")
     cfg.MODEL.VIT_TYPE = vit
     cfg.MODEL.HIDDEN_DIM = hidden or (1024 if vit == "large_patch16" else 768)
     cfg.MODEL.HEAD_TYPE = "CORNER_UP"
-    cfg.MODEL.FUSION_CLASS = "Attention_Fusion_Bimodal_LNSpecific"
+    cfg.MODEL.FUSION_CLASS = fusion_class
     cfg.MODEL.FUSION_LAYERS = fusion_layers
     cfg.MODEL.BACKBONE.PRETRAINED = False
     cfg.MODEL.RGBT_PRETRAINED_PATH = ""
@@ -696,10 +800,11 @@ def hot_path_cfg(vit="base_patch16", search=320, template=128, fusion_layers=2, 
     return cfg
 
 
-def reference_state_dict_shapes(variant, hidden=768, depth=12, search=320, template=128, fusion_layers=2):
+def reference_state_dict_shapes(variant, hidden=768, depth=12, search=320, template=128, fusion_layers=2,
+                                fusion_class="Attention_Fusion_Bimodal_LNSpecific"):
     """(name, shape) of the reference state_dict, built on the meta device (no memory)."""
     vit = {768: "base_patch16", 1024: "large_patch16"}[hidden]
-    cfg = hot_path_cfg(vit, search, template, fusion_layers)
+    cfg = hot_path_cfg(vit, search, template, fusion_layers, fusion_class=fusion_class)
     with torch.device("meta"):
         m = BUILDERS[variant](cfg, train=False)
     return [(k, list(v.shape)) for k, v in m.state_dict().items()]

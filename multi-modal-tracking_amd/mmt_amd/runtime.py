@@ -28,7 +28,8 @@ import torch
 from . import _lib
 from ._lib import LIB, GemmParams, AttnParams, SlotCopySeg, check, MMT_F32, MMT_BF16, MMT_F16
 
-VARIANTS = ("rgbt", "shared", "asym", "asym_online", "asym_ce", "rgb")  # rgb: RGB-only MixFormer (config 1)
+# rgb: RGB-only MixFormer (config 1); uni: "shared" on blocks with one norm1 / norm2 for both modalities
+VARIANTS = ("rgbt", "shared", "asym", "asym_online", "asym_ce", "rgb", "uni")
 
 
 LOG2E = 1.4426950408889634
@@ -57,7 +58,8 @@ class Dims:
         self.hidden = sd[pre + "blocks.0.mlp.fc1.weight"].shape[0]
         self.nmod = 1 if variant == "rgb" else 2  # modalities (sequences per frame)
         fusion = self.nmod == 2  # the RGB-only model has no fusion: the head reads the backbone
-        self.d_model = sd["fusion_vi.adjust_v.0.weight"].shape[0] if fusion else 512
+        adj = "fusion_vi.adjust_in.0.weight" if "fusion_vi.adjust_in.0.weight" in sd else "fusion_vi.adjust_v.0.weight"
+        self.d_model = sd[adj].shape[0] if fusion else 512
         self.fusion_layers = 0
         while fusion and ("fusion_vi.fusion_attention.encoder.layers.%d.linear1.weight" % self.fusion_layers) in sd:
             self.fusion_layers += 1
@@ -67,7 +69,7 @@ class Dims:
 
 
 class MixFormerRGBTRuntime:
-    """Compiled forward of one of the four hot-path variants on the current CUDA (HIP) device."""
+    """Compiled forward of one of the VARIANTS on the current CUDA (HIP) device."""
 
     gemm_impl = 0  # mmt_gemm_params.impl of every plan GEMM (0 = library's choice; A/B knob)
     gemm_splitk = 0  # mmt_gemm_params.splitk of every plan GEMM (0 = library's choice, 1 = off)
@@ -154,6 +156,9 @@ class MixFormerRGBTRuntime:
         C = d.C
         pres = ["backbone_v.", "backbone_i."] if self.variant == "rgbt" else ["backbone."]
         single_ln = self.variant in ("rgbt", "rgb")  # norm1 / norm2 (else per-modality norm*_v / norm*_i)
+        # uni: the shared plan on blocks whose one norm1 / norm2 serves both modalities; both modality groups
+        # get the SAME device tensors (norms and LayerNorm-folded weights), not copies
+        tied_ln = self.variant == "uni"
         W["bb"] = []
         for pre in pres:
             bb = {"patch_w": self._T(sd[pre + "patch_embed.proj.weight"].reshape(C, -1)),
@@ -170,6 +175,9 @@ class MixFormerRGBTRuntime:
                 if single_ln:
                     for nm in ("norm1", "norm2"):
                         blk[nm] = (self._F(sd[b + nm + ".weight"]), self._F(sd[b + nm + ".bias"]))
+                elif tied_ln:
+                    for nm in ("norm1", "norm2"):
+                        blk[nm + "_v"] = blk[nm + "_i"] = (self._F(sd[b + nm + ".weight"]), self._F(sd[b + nm + ".bias"]))
                 else:
                     for nm in ("norm1", "norm2"):
                         blk[nm + "_v"] = (self._F(sd[b + nm + "_v.weight"]), self._F(sd[b + nm + "_v.bias"]))
@@ -178,7 +186,7 @@ class MixFormerRGBTRuntime:
                     # Linear(LayerNorm(x)) = rstd*(x.W' - mu*colsum(W')) + b', W' = W*gamma (per k),
                     # b' = b + W.beta; one (W', colsum, b') per norm (two-stream: this backbone's;
                     # shared: norm*_v / norm*_i -> one GEMM group per modality)
-                    norms = ["", ] if single_ln else ["_v", "_i"]
+                    norms = ["", ] if single_ln or tied_ln else ["_v", "_i"]
                     for lin, nm in (("attn.qkv", "norm1"), ("mlp.fc1", "norm2")):
                         w64, b64 = sd[b + lin + ".weight"].double(), sd[b + lin + ".bias"].double()
                         if lin == "attn.qkv":
@@ -194,6 +202,8 @@ class MixFormerRGBTRuntime:
                             fw.append(wt)
                             fc.append(self._F(wt.double().sum(1)))
                             fb.append(self._F(b64 + w64 @ bet))
+                        if tied_ln:
+                            fw, fc, fb = fw * 2, fc * 2, fb * 2
                         blk[lin + ".fw"], blk[lin + ".fcs"], blk[lin + ".fb"] = fw, fc, fb
                 bb["blocks"].append(blk)
             W["bb"].append(bb)
@@ -204,13 +214,34 @@ class MixFormerRGBTRuntime:
         d, W = self.d, self.w
         C = d.C
         f = "fusion_vi."
-        for m in ("v", "i"):
-            W["adj_" + m + ".w"] = self._T(sd[f + "adjust_%s.0.weight" % m].reshape(d.d_model, C))
-            W["adj_" + m + ".b"] = self._F(sd[f + "adjust_%s.0.bias" % m])
-            W["adj_" + m + ".gn"] = (self._F(sd[f + "adjust_%s.1.weight" % m]), self._F(sd[f + "adjust_%s.1.bias" % m]))
-        W["adj_cat.w"] = self._T(sd[f + "adjust_cat.0.weight"].reshape(C, 2 * d.d_model))
-        W["adj_cat.b"] = self._F(sd[f + "adjust_cat.0.bias"])
-        W["adj_cat.gn"] = (self._F(sd[f + "adjust_cat.1.weight"]), self._F(sd[f + "adjust_cat.1.bias"]))
+        # The front-end is read from the keys present.  Each of the reference's deformable front-ends is
+        # Attention_Fusion_Bimodal_LNSpecific with some weights tied (fusion_utils.py:165-353), so all of them
+        # fill the same W[...] entries and run the same launch list; a tied pair is one device tensor:
+        #   adjust_in (LNSpecific_2)                -> adj_v = adj_i
+        #   adjust_sum / adjust_out on out_v + out_i -> adj_cat = [W | W] along the input channels
+        #                                               (W.(a + b) = [W | W].[a ; b], the split-A GEMM as it is)
+        #   encoder norm1 / norm2 (Bimodal)         -> norm*_v = norm*_i
+        tail = [t for t in ("adjust_cat", "adjust_sum", "adjust_out") if f + t + ".0.weight" in sd]
+        if len(tail) != 1:
+            raise KeyError("fusion_vi: expected one of adjust_cat / adjust_sum / adjust_out, found %s" % tail)
+        tail = tail[0]
+        one_in = f + "adjust_in.0.weight" in sd
+        for m in ("v",) if one_in else ("v", "i"):
+            a = f + ("adjust_in" if one_in else "adjust_" + m)
+            W["adj_" + m + ".w"] = self._T(sd[a + ".0.weight"].reshape(d.d_model, C))
+            W["adj_" + m + ".b"] = self._F(sd[a + ".0.bias"])
+            W["adj_" + m + ".gn"] = (self._F(sd[a + ".1.weight"]), self._F(sd[a + ".1.bias"]))
+        if one_in:
+            for k in (".w", ".b", ".gn"):
+                W["adj_i" + k] = W["adj_v" + k]
+        wt = sd[f + tail + ".0.weight"].reshape(C, -1)
+        if tail != "adjust_cat":
+            wt = torch.cat([wt, wt], 1)
+        if wt.shape[1] != 2 * d.d_model:
+            raise ValueError("fusion_vi.%s.0.weight: %d input channels" % (tail, sd[f + tail + ".0.weight"].shape[1]))
+        W["adj_cat.w"] = self._T(wt)
+        W["adj_cat.b"] = self._F(sd[f + tail + ".0.bias"])
+        W["adj_cat.gn"] = (self._F(sd[f + tail + ".1.weight"]), self._F(sd[f + tail + ".1.bias"]))
         fa = f + "fusion_attention."
         W["level_embed"] = self._F(sd[fa + "level_embed"])
         W["enc"] = []
@@ -223,8 +254,12 @@ class MixFormerRGBTRuntime:
                  "out.w": self._T(sd[sa + "output_proj.weight"]), "out.b": self._F(sd[sa + "output_proj.bias"]),
                  "l1.w": self._T(sd[lp + "linear1.weight"]), "l1.b": self._F(sd[lp + "linear1.bias"]),
                  "l2.w": self._T(sd[lp + "linear2.weight"]), "l2.b": self._F(sd[lp + "linear2.bias"])}
-            for nm in ("norm1_v", "norm1_i", "norm2_v", "norm2_i"):
-                e[nm] = (self._F(sd[lp + nm + ".weight"]), self._F(sd[lp + nm + ".bias"]))
+            if lp + "norm1.weight" in sd:  # the plain encoder layer: one norm for both modalities
+                for nm in ("norm1", "norm2"):
+                    e[nm + "_v"] = e[nm + "_i"] = (self._F(sd[lp + nm + ".weight"]), self._F(sd[lp + nm + ".bias"]))
+            else:
+                for nm in ("norm1_v", "norm1_i", "norm2_v", "norm2_i"):
+                    e[nm] = (self._F(sd[lp + nm + ".weight"]), self._F(sd[lp + nm + ".bias"]))
             W["enc"].append(e)
         W["pos_sine"] = self._F(_sine_pos(d.gs, d.d_model))  # [ns][512]
         # The encoder query is src + (pos + level_embed[l]) per modality l (deformable_transformer

@@ -33,7 +33,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from .model import FrozenBatchNorm2d
+from .model import FrozenBatchNorm2d, fusion_parts, layer_norms
 
 LOG2E = 1.4426950408889634
 
@@ -239,6 +239,35 @@ class _HipLinear(torch.autograd.Function):
         # K of dy^T [x | 1] is sum_m dy[m][n] (the same bf16 dy, fp32 accumulation; no reduce kernel)
         dw, db = _weight_grads(dy, x, M, N, K)
         return dx, dw, db, None
+
+
+class _HipLinearDup(torch.autograd.Function):
+    """y = x [W | W]^T + b: a Linear on the sum of x's two column halves, W.(a + b) = [W | W].[a ; b] (the fusion's
+    adjust_sum / adjust_out on out_v + out_i, fusion_utils.py:315-317, :350-352), run as the GEMM of the concat
+    form so that it is the very call Attention_Fusion_Bimodal_LNSpecific's adjust_cat makes.  x [M][2K] bf16,
+    W [N][K] fp32 master.  Two aten launches besides _HipLinear's: the cat of the bf16 weight (forward) and the
+    add of dW's two halves (backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, out_f32=False):
+        M, K2 = x.shape
+        N = w.shape[0]
+        x = x.contiguous()
+        wb = _bf16_weight(w)
+        wb = torch.cat([wb, wb], 1)
+        y = _gemm(x, wb, M, N, K2, bias=b.detach().float().contiguous(), out_f32=out_f32)
+        ctx.save_for_backward(x, wb)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wb = ctx.saved_tensors
+        M, K2 = x.shape
+        N = wb.shape[0]
+        dy = dy.to(torch.bfloat16).contiguous()
+        dx = _dx(dy, wb, M, N, K2) if ctx.needs_input_grad[0] else None
+        dw, db = _weight_grads(dy, x, M, N, K2)
+        return dx, dw[:, :K2 // 2] + dw[:, K2 // 2:], db, None
 
 
 class _HipMlp(torch.autograd.Function):
@@ -1366,13 +1395,21 @@ class _HipAddUp(torch.autograd.Function):
         return da, dout, None
 
 
-def _adjust_tokens(ops, seq, tok):
+def _adjust_tokens(ops, seq, tok, summed=False):
     """nn.Sequential(Conv2d 1x1, GroupNorm) of the fusion (fusion_utils.py:252-268) on token rows
-    tok [B][P][Cin] -> [B][P][Cout] fp32: the 1x1 conv as ops.linear (HIP GEMM) and ops.group_norm."""
+    tok [B][P][Cin] -> [B][P][Cout] fp32: the 1x1 conv as ops.linear (HIP GEMM) and ops.group_norm.
+    summed: the conv reads the sum of tok's two channel halves (adjust_sum / adjust_out on out_v + out_i,
+    fusion_utils.py:315-317, :350-352) as [W | W] on their concat, W.(a + b) = [W | W].[a ; b]: the same GEMM
+    call as adjust_cat's (ops.linear_dup; stand-in ops: the cat of W, whose backward sums the halves' gradients)."""
     conv, gn = seq[0], seq[1]
     B, P, Cin = tok.shape
-    w = conv.weight.view(conv.weight.shape[0], Cin)
-    y = ops.linear(tok.reshape(B * P, Cin).to(ops.dtype).contiguous(), w, conv.bias, out_f32=True)
+    w = conv.weight.view(conv.weight.shape[0], -1)
+    lin = ops.linear
+    if summed:
+        lin = getattr(ops, "linear_dup", None)
+        if lin is None:
+            lin, w = ops.linear, torch.cat([w, w], 1)
+    y = lin(tok.reshape(B * P, Cin).to(ops.dtype).contiguous(), w, conv.bias, out_f32=True)
     return ops.group_norm(y.view(B, P, -1), gn.weight, gn.bias, gn.num_groups, gn.eps)
 
 
@@ -1433,6 +1470,11 @@ class HipOps:
     @staticmethod
     def linear(x, weight, bias, out_f32=False):
         return _HipLinear.apply(x, weight, bias, out_f32)
+
+    @staticmethod
+    def linear_dup(x, weight, bias, out_f32=False):
+        """Linear on the sum of x's two column halves as x [W | W]^T + b (_HipLinearDup)."""
+        return _HipLinearDup.apply(x, weight, bias, out_f32)
 
     @staticmethod
     def group_norm(x, w, b, groups, eps):
@@ -1868,7 +1910,8 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
 
     for li, blk in enumerate(bb.blocks):
         dp = drop_path_rate * li / max(depth - 1, 1)
-        xn, xr = ln2(x, blk.norm1_v, blk.norm1_i)
+        n1, n2 = layer_norms(blk)  # one module twice in the uni-backbone's plain blocks
+        xn, xr = ln2(x, *n1)
         qkv = ops.linear(xn.view(B2 * n, C), blk.attn.qkv.weight, blk.attn.qkv.bias).view(B2, n, 3 * C)
         a = ops.mam_attention_asym(qkv, Bh, n_t, H) if asym else ops.mam_attention(qkv, n_t, H)
         x = _branch_residual(ops, xr, a.reshape(B2 * n, C), blk.attn.proj, dp, bb.training)
@@ -1884,7 +1927,7 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
                 x = _ce_rows_gather(ops, x, torch.cat([head, order.to(torch.int32) + n_t], 1))
                 n = n_t + keep
             stage += 1
-        xn, xr = ln2(x, blk.norm2_v, blk.norm2_i)
+        xn, xr = ln2(x, *n2)
         x = _mlp_residual(ops, xr, xn.view(B2 * n, C), blk.mlp, dp, bb.training)
     if gidx is not None:  # _recover_search: row n_t + gidx[j] of the full stream is row n_t + j, zeros elsewhere
         head = _const(("ce_head", B2, n_t), x.device, lambda: torch.arange(n_t, dtype=torch.int32).repeat(B2, 1))
@@ -1919,17 +1962,21 @@ def _ref_points(H, W, B, L, device):
 def fusion_forward(fu, s_v, s_i, ops):
     """Attention_Fusion_Bimodal_LNSpecific.forward (fusion_utils.py:270-279) with the deformable
     encoder (deformable_encoder_lnspecific.py:131-160) and MSDeformAttn_Bimodal
-    (ms_deform_attn_bimodal.py:83-130)."""
+    (ms_deform_attn_bimodal.py:83-130).  The other deformable front-ends (Attention_Fusion_Bimodal,
+    _LNSpecific_Sum, _LNSpecific_2; fusion_utils.py:165-353) are this one with weights tied: model.fusion_parts /
+    layer_norms hand the same module for both modalities and the grouped ops get its Parameters twice, so autograd
+    sums the two gradients into them; the summed tail runs as [W | W] on the concat (_adjust_tokens)."""
+    adj_v, adj_i, tail, summed = fusion_parts(fu)
     tokens = getattr(ops, "group_norm", None) is not None  # adjust_* on token rows (HIP GEMM + GroupNorm)
     if s_i is None:  # both modalities' search tokens as bf16 rows (2B, ns, C) (_backbones_rgbt tokens=True)
         b, P, Cin = s_v.shape[0] // 2, s_v.shape[1], s_v.shape[2]
         h = w = int(round(P ** 0.5))
         if not tokens or h * w != P or getattr(ops, "linear2", None) is None:
             raise ValueError("fusion_forward: token-row inputs need the grouped token-row adjust (HipOps), square maps")
-        cv, ci = fu.adjust_v[0], fu.adjust_i[0]
+        cv, ci = adj_v[0], adj_i[0]
         y = ops.linear2(s_v.view(2 * b * P, Cin), cv.weight.view(cv.weight.shape[0], Cin), cv.bias,
                         ci.weight.view(ci.weight.shape[0], Cin), ci.bias, out_f32=True)
-        gv, gi = fu.adjust_v[1], fu.adjust_i[1]
+        gv, gi = adj_v[1], adj_i[1]
         if (gv.num_groups, gv.eps) != (gi.num_groups, gi.eps):
             raise ValueError("fusion_forward: the two adjust GroupNorms differ in groups / eps")
         av, ai = _HipGroupNorm2.apply(y.view(2 * b, P, -1), gv.weight, gv.bias, gi.weight, gi.bias, gv.num_groups,
@@ -1938,13 +1985,13 @@ def fusion_forward(fu, s_v, s_i, ops):
         src = torch.cat([av, ai], 1)
     elif tokens:
         b, _, h, w = s_v.shape
-        av = _adjust_tokens(ops, fu.adjust_v, s_v.flatten(2).transpose(1, 2))
-        ai = _adjust_tokens(ops, fu.adjust_i, s_i.flatten(2).transpose(1, 2))
+        av = _adjust_tokens(ops, adj_v, s_v.flatten(2).transpose(1, 2))
+        ai = _adjust_tokens(ops, adj_i, s_i.flatten(2).transpose(1, 2))
         d = av.shape[2]
         src = torch.cat([av, ai], 1)
     else:
         b, _, h, w = s_v.shape
-        av, ai = fu.adjust_v(s_v), fu.adjust_i(s_i)
+        av, ai = adj_v(s_v), adj_i(s_i)
         d = av.shape[1]
         src = torch.cat([av.flatten(2).transpose(1, 2), ai.flatten(2).transpose(1, 2)], 1)
     fa = fu.fusion_attention
@@ -1994,16 +2041,19 @@ def fusion_forward(fu, s_v, s_i, ops):
         src2 = lin(sa.output_proj, ops.ms_deform_attn(value.float().contiguous(), h, loc.contiguous(), aw.contiguous()))
         src2 = torch.cat([src2, src2], 1)
         src = src + layer.dropout1(src2)
-        src = _ln_halves(ops, src, layer.norm1_v, layer.norm1_i)
+        n1, n2 = layer_norms(layer)
+        src = _ln_halves(ops, src, *n1)
         src = src + layer.dropout3(lin(layer.linear2, layer.dropout2(F.relu(lin(layer.linear1, src)))))
-        src = _ln_halves(ops, src, layer.norm2_v, layer.norm2_i)
+        src = _ln_halves(ops, src, *n2)
     o_v, o_i = torch.chunk(src, 2, 1)
     if tokens:  # channel concat on token rows, then back to NCHW for the corner head's convolutions
-        y = _adjust_tokens(ops, fu.adjust_cat, torch.cat([o_v, o_i], 2))
+        y = _adjust_tokens(ops, tail, torch.cat([o_v, o_i], 2), summed)
         return y.transpose(1, 2).reshape(b, -1, h, w)
     o_v = o_v.permute(0, 2, 1).reshape(b, -1, h, w)
     o_i = o_i.permute(0, 2, 1).reshape(b, -1, h, w)
-    return fu.adjust_cat(torch.cat([o_v, o_i], 1))
+    if summed:  # the same [W | W] form on the aten path
+        return tail[1](F.conv2d(torch.cat([o_v, o_i], 1), torch.cat([tail[0].weight] * 2, 1), tail[0].bias))
+    return tail(torch.cat([o_v, o_i], 1))
 
 
 def _encoder_layer_hip(layer, src, lpos, ref_q, hw, li):
@@ -2024,10 +2074,11 @@ def _encoder_layer_hip(layer, src, lpos, ref_q, hw, li):
     ms = HipOps.msda_bimodal(value, offw, ref_q, hw)
     src2 = HipOps.linear(ms.view(M // 2, d), sa.output_proj.weight, sa.output_proj.bias).view(B, n2 // 2, d)
     src = _HipDropResidual.apply(src, src2, drop(layer.dropout1), 8 * li + 1, True)
-    src = _ln_halves(HipOps, src, layer.norm1_v, layer.norm1_i)
+    norm1, norm2 = layer_norms(layer)
+    src = _ln_halves(HipOps, src, *norm1)
     src = _HipEncoderFFN.apply(src.view(M, d), layer.linear1.weight, layer.linear1.bias, layer.linear2.weight,
                                layer.linear2.bias, drop(layer.dropout2), drop(layer.dropout3), 8 * li + 1)
-    return _ln_halves(HipOps, src.view(B, n2, d), layer.norm2_v, layer.norm2_i)
+    return _ln_halves(HipOps, src.view(B, n2, d), *norm2)
 
 
 def _ln_halves(ops, src, nv, ni):
@@ -2226,7 +2277,7 @@ def module_forward(net, template, online_template, search, ops, run_score_head=F
     """The drop-in module's forward with autograd (net.train() under grad mode; what the reference's
     MixFormerRGBTActor calls, actors/mixformer_rgbt.py:82-98, possibly wrapped in DDP + SyncBN,
     train_script_mixformer.py:105-110): MixFormer_RGBT.forward (mixformer.py:366-395),
-    mixformer_shared.py:400-424, asymmetric_shared.py:349-368 and asymmetric_shared_online.py:351-413
+    mixformer_shared.py:400-424, mixformer_unibackbone.py:367-394, asymmetric_shared.py:349-368 and asymmetric_shared_online.py:351-413
     (score head on the predicted boxes: gt_bboxes is accepted and ignored, as the reference's forward
     drops it at asymmetric_shared_online.py:374), and asymmetric_shared_ce.py:557-587 (variant asym_ce:
     candidate elimination at net.ce_loc / net.ce_keep_ratio with the actor's ce_template_mask / ce_keep_rate,
@@ -2239,9 +2290,10 @@ def module_forward(net, template, online_template, search, ops, run_score_head=F
     if variant == "rgbt":
         s_v, s_i = _backbones_rgbt(net, template, online_template, search, ops, dpr, tokens=_token_rows(ops))
         tok = None
-    elif variant in ("shared", "asym", "asym_online"):
+    elif variant in ("shared", "uni", "asym", "asym_online"):  # uni: the shared route on plain blocks (layer_norms)
         feats, tok = backbone_forward_stacked(net.backbone, torch.cat(template, 0), torch.cat(online_template, 0),
-                                              torch.cat(search, 0), ops, asym=variant != "shared", drop_path_rate=dpr)
+                                              torch.cat(search, 0), ops, asym=variant not in ("shared", "uni"),
+                                              drop_path_rate=dpr)
         s_v, s_i = feats.chunk(2, 0)
     elif variant == "asym_ce":
         feats, tok = backbone_forward_stacked(net.backbone, torch.cat(template, 0), torch.cat(online_template, 0),
