@@ -40,6 +40,9 @@
  *   mmt_conv3x3_c1 / mmt_conv3x3_c1_pair  the 1-channel conv-BN-ReLU of adjust3/adjust4,
  *       head.py:115-120 (the pair form runs adjust3[2] and adjust4[1] in one launch)
  *   mmt_spm_attention           ScoreDecoder single-query attention, score_decoder.py:55-61
+ *   mmt_spm_attention_train_fwd / mmt_spm_attention_bwd / mmt_spm_dq_sum / mmt_bce_logits / _bwd  the same
+ *       attention with its softmax rows kept, its backward, and the BCE-with-logits loss of the TRAIN_SCORE
+ *       stage, score_decoder.py:32-66, actors/mixformer_rgbt.py:150-152
  *   mmt_ce_t2s_attention / mmt_ce_select / mmt_ce_gather / mmt_ce_recover  candidate elimination
  *       of asymmetric_shared_ce.py:22-102, :198-202, :426-447 (attn_t2s mean, sorted top-k, recover)
  *   mmt_ce_rows_gather / mmt_ce_index_invert  the same elimination under autograd (training): pruning, recovery and
@@ -475,6 +478,30 @@ int mmt_prroi_pool_coor_backward(const float* features, const float* rois, const
  * H heads of C/H (= 64), scale; out [B][C] fp32 (dtype copy optional via out_t). */
 int mmt_spm_attention(const float* q, int64_t q_stride, const float* kv, float* out, int B, int Lk, int C, int H,
                       float scale, void* stream);
+
+/* Score-head training (TRAIN.TRAIN_SCORE: lib/train/train_script_mixformer.py:138-140, actors/mixformer_rgbt.py:150-152;
+ * the decoder is lib/models/mixformer_cvt/score_decoder.py:32-66), fp32 in and out, no atomics, fixed summation
+ * orders (two launches give the same bits).  Every entry point rejects (MMT_EBADARG) null pointers, B <= 0,
+ * Lk <= 0, Lk > 2048 (mmt_spm_attention's key cap), C != 64 H and a q_stride other than 0 or C.
+ *   mmt_spm_attention_train_fwd: mmt_spm_attention's layouts and arithmetic (q [B][C] with q_stride C, or one
+ *     shared row with q_stride 0; kv [B][Lk][2C] = k | v); out [B][C] has mmt_spm_attention's bits, and the
+ *     normalised softmax rows go to prob [B][H][Lk].
+ *   mmt_spm_attention_bwd: with dp_j = dout_h . v_j and ds_j = prob_j (dp_j - sum_i prob_i dp_i):
+ *     dv_j = prob_j dout_h, dk_j = scale ds_j q_h (dkv [B][Lk][2C] = dk | dv), dq_h = scale sum_j ds_j k_j
+ *     (dq [B][C], one row per batch row also when q_stride is 0).  dkv and dq are written in full.
+ *   mmt_spm_dq_sum: out [C] = the B rows of dq [B][C] added in row order (the gradient of the shared query row).
+ *   mmt_bce_logits: loss[0] = weight * mean_i l(x_i, y_i), l = (1 - y) x + m + log(exp(-m) + exp(-x - m)),
+ *     m = max(-x, 0) (torch.nn.BCEWithLogitsLoss; evaluated as max(-x, 0) + log1p(exp(-|x|))); labels fp32 in
+ *     [0, 1]; one workgroup, 1 <= B <= 65536.
+ *   mmt_bce_logits_bwd: dlogits_i = dloss[0] * weight * (sigmoid(x_i) - y_i) / B, same B range. */
+int mmt_spm_attention_train_fwd(const float* q, int64_t q_stride, const float* kv, float* out, float* prob, int B,
+                                int Lk, int C, int H, float scale, void* stream);
+int mmt_spm_attention_bwd(const float* q, int64_t q_stride, const float* kv, const float* prob, const float* dout,
+                          float* dq, float* dkv, int B, int Lk, int C, int H, float scale, void* stream);
+int mmt_spm_dq_sum(const float* dq, float* out, int B, int C, void* stream);
+int mmt_bce_logits(const float* logits, const float* labels, float weight, float* loss, int B, void* stream);
+int mmt_bce_logits_bwd(const float* logits, const float* labels, const float* dloss, float weight, float* dlogits,
+                       int B, void* stream);
 
 /* ---------------------------------------------------------------- tracker pre/post-processing
  * mmt_sample_target replaces the per-frame host path of the RGB-T trackers

@@ -131,6 +131,11 @@ _PROTOS = {
     "mmt_prroi_pool_backward": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mmt_prroi_pool_coor_backward": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
     "mmt_spm_attention": [vp, i64, vp, vp, i32, i32, i32, i32, f32, vp],
+    "mmt_spm_attention_train_fwd": [vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "mmt_spm_attention_bwd": [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "mmt_spm_dq_sum": [vp, vp, i32, i32, vp],
+    "mmt_bce_logits": [vp, vp, f32, vp, i32, vp],
+    "mmt_bce_logits_bwd": [vp, vp, vp, f32, vp, i32, vp],
     "mmt_ce_t2s_attention": [vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp],
     "mmt_ce_t2s_attention_masked": [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp],
     "mmt_ce_select": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp],

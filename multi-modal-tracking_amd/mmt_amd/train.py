@@ -122,8 +122,9 @@ def _account(M, N, K, G, a_bytes, w_bytes, c_bytes, extra_bytes=0):
 
 
 def _gemm(a, w, M, N, K, bias=None, out_f32=False, act=0, r=None, c2=None, c2_copy=0, c=None, ldc=None, a_t=0,
-          w_t=0, ldw=0, lda=None, splitk=False, impl=0, row_scale=None, row_scale_div=1, nsk=0):
-    """C[M][N] = A[M][K] W[N][K]^T (+ bias), bf16 operands, fp32 accumulation (mmt_gemm); act / r (bf16,
+          w_t=0, ldw=0, lda=None, splitk=False, impl=0, row_scale=None, row_scale_div=1, nsk=0, f32=False):
+    """C[M][N] = A[M][K] W[N][K]^T (+ bias), bf16 operands, fp32 accumulation (mmt_gemm; f32: fp32 operands and
+    an fp32 output, the plain GEMM only); act / r (bf16,
     [M][N]) / c2 / c2_copy as mmt_gemm_params (act 1 GELU, 5 GELU backward against r; c2_copy 2: c2 = the
     pre-activation; 3: the last 8 columns to c2 [M][8]; 4: column N - 8 alone to c2 [M]); c / ldc: a
     preallocated output and its pitch;
@@ -131,7 +132,7 @@ def _gemm(a, w, M, N, K, bias=None, out_f32=False, act=0, r=None, c2=None, c2_co
     workspace (the cost model may split K over workgroups; nsk >= 1 forces the slice count, A/B tools).
     Grouped form (the two-stream backbones in lockstep): a and w (and bias / r / c2 / c) tuples, one entry
     per group, one launch; without c the output is one [groups * M][N] tensor, group g on rows g M ..."""
-    from ._lib import LIB, GemmParams, MMT_BF16, check
+    from ._lib import LIB, GemmParams, MMT_BF16, MMT_F32, check
     grouped = isinstance(a, tuple)
     A, W = (a, w) if grouped else ((a,), (w,))
     G = len(A)
@@ -167,7 +168,7 @@ def _gemm(a, w, M, N, K, bias=None, out_f32=False, act=0, r=None, c2=None, c2_co
         for g, t in enumerate(c2 if grouped else (c2,)):
             p.c2[g] = t.data_ptr()
         p.c2_copy = c2_copy
-    check(LIB.mmt_gemm(p, MMT_BF16, _stream()), "mmt_gemm")
+    check(LIB.mmt_gemm(p, MMT_F32 if f32 else MMT_BF16, _stream()), "mmt_gemm")
     if GEMM_ACCOUNT is not None:
         extra = G * N * 4 if bias is not None else 0
         if r is not None:
@@ -175,7 +176,7 @@ def _gemm(a, w, M, N, K, bias=None, out_f32=False, act=0, r=None, c2=None, c2_co
         if c2 is not None:
             t2 = c2 if not grouped else c2[0]
             extra += G * t2.numel() * t2.element_size()
-        _account(M, N, K, G, 2, 2, 4 if out_f32 else 2, extra)
+        _account(M, N, K, G, 4 if f32 else 2, 4 if f32 else 2, 4 if out_f32 else 2, extra)
     return c
 
 
@@ -216,7 +217,9 @@ def _dx(dy, wb, M, N, K, act=0, r=None):
 
 class _HipLinear(torch.autograd.Function):
     """y = x W^T + b (nn.Linear) with bf16 operands; x [M][K] bf16, W [N][K] fp32 master, b [N]; y bf16,
-    or fp32 straight from the GEMM's accumulators (out_f32: the residual-stream adds, no cast pass)."""
+    or fp32 straight from the GEMM's accumulators (out_f32: the residual-stream adds, no cast pass).
+    An fp32 x (the score decoder, which the inference plan too keeps in fp32) runs the forward as an fp32 GEMM on
+    the master weight, y fp32; the backward is the same either way, on bf16(x) and the bf16 weight."""
 
     @staticmethod
     def forward(ctx, x, w, b, out_f32=False):
@@ -224,6 +227,11 @@ class _HipLinear(torch.autograd.Function):
         N = w.shape[0]
         x = x.contiguous()
         wb = _bf16_weight(w)  # bf16 shadow written by HipAdamW's update (same values)
+        if x.dtype == torch.float32:
+            y = _gemm(x, w.detach().contiguous(), M, N, K, bias=b.detach().float().contiguous(), out_f32=True,
+                      f32=True)
+            ctx.save_for_backward(x.to(torch.bfloat16), wb)
+            return y
         y = _gemm(x, wb, M, N, K, bias=b.detach().float().contiguous(), out_f32=out_f32)
         ctx.save_for_backward(x, wb)
         return y
@@ -1281,17 +1289,22 @@ class _HipEncoderFFN(torch.autograd.Function):
 class _HipLinearCat(torch.autograd.Function):
     """Two nn.Linear layers on the same input as one GEMM (the bimodal query's sampling_offsets and
     attention_weights, ms_deform_attn_bimodal.py:99-100): y = x [W0; W1]^T + [b0; b1] (bf16 x (M, K) -> bf16
-    (M, N0 + N1)); one dX GEMM (the two input gradients summed in its K loop) and one dW GEMM, whose rows are the
-    two weights' gradients."""
+    (M, N0 + N1), fp32 with out_f32 or from an fp32 x: the score decoder's k | v); one dX GEMM (the two input
+    gradients summed in its K loop) and one dW GEMM, whose rows are the two weights' gradients."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1):
+    def forward(ctx, x, w0, b0, w1, b1, out_f32=False):
         M, K = x.shape
         N0, N1 = w0.shape[0], w1.shape[0]
         x = x.contiguous()
         wb = torch.cat([_bf16_weight(w0), _bf16_weight(w1)], 0)
         bias = torch.cat([b0.detach().float(), b1.detach().float()], 0)
-        y = _gemm(x, wb, M, N0 + N1, K, bias=bias)
+        if x.dtype == torch.float32:  # fp32 forward on the master weights, as _HipLinear's
+            y = _gemm(x, torch.cat([w0.detach(), w1.detach()], 0), M, N0 + N1, K, bias=bias, out_f32=True, f32=True)
+            ctx.save_for_backward(x.to(torch.bfloat16), wb)
+            ctx.n0 = N0
+            return y
+        y = _gemm(x, wb, M, N0 + N1, K, bias=bias, out_f32=out_f32)
         ctx.save_for_backward(x, wb)
         ctx.n0 = N0
         return y
@@ -1305,7 +1318,7 @@ class _HipLinearCat(torch.autograd.Function):
         dx = _dx(dy, wb, M, N, K) if ctx.needs_input_grad[0] else None
         dw, db = _weight_grads(dy, x, M, N, K)
         n0 = ctx.n0
-        return dx, dw[:n0], db[:n0], dw[n0:], db[n0:]
+        return dx, dw[:n0], db[:n0], dw[n0:], db[n0:], None
 
 
 class _HipCornerBoxes(torch.autograd.Function):
@@ -1364,6 +1377,77 @@ class _HipBoxLoss(torch.autograd.Function):
         check(LIB.mmt_box_loss_bwd(pred.data_ptr(), gt.data_ptr(), dout.data_ptr(), dpred.data_ptr(), pred.shape[0],
                                    *ctx.w, _stream()), "mmt_box_loss_bwd")
         return dpred, None, None, None
+
+
+class _HipSpmAttention(torch.autograd.Function):
+    """The ScoreDecoder's single-query attention (score_decoder.py:55-61): q (B, C) fp32, or (1, C) for a query
+    row every batch row shares (decoder layer 0's score token), kv (B, Lk, 2C) fp32 = k | v -> (B, C) fp32
+    (mmt_spm_attention_train_fwd, which keeps the softmax rows; backward mmt_spm_attention_bwd, and for the
+    shared row mmt_spm_dq_sum: its B gradient rows added in row order)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads, scale):
+        from ._lib import LIB, check
+        B, Lk, C2 = kv.shape
+        C = C2 // 2
+        if q.shape not in ((1, C), (B, C)):
+            raise ValueError("HIP spm_attention: q (1, C) or (B, C) against kv (B, Lk, 2C)")
+        q, kv = q.detach().float().contiguous(), kv.detach().float().contiguous()
+        qs = C if q.shape[0] == B else 0
+        out = torch.empty(B, C, device=kv.device, dtype=torch.float32)
+        prob = torch.empty(B, heads, Lk, device=kv.device, dtype=torch.float32)
+        check(LIB.mmt_spm_attention_train_fwd(q.data_ptr(), qs, kv.data_ptr(), out.data_ptr(), prob.data_ptr(), B, Lk,
+                                              C, heads, float(scale), _stream()), "mmt_spm_attention_train_fwd")
+        ctx.save_for_backward(q, kv, prob)
+        ctx.args = (qs, heads, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from ._lib import LIB, check
+        q, kv, prob = ctx.saved_tensors
+        qs, heads, scale = ctx.args
+        B, Lk, C2 = kv.shape
+        C = C2 // 2
+        dout = dout.float().contiguous()
+        dq, dkv = torch.empty(B, C, device=kv.device, dtype=torch.float32), torch.empty_like(kv)
+        check(LIB.mmt_spm_attention_bwd(q.data_ptr(), qs, kv.data_ptr(), prob.data_ptr(), dout.data_ptr(),
+                                        dq.data_ptr(), dkv.data_ptr(), B, Lk, C, heads, scale, _stream()),
+              "mmt_spm_attention_bwd")
+        if q.shape[0] != B:
+            rows, dq = dq, torch.empty(1, C, device=kv.device, dtype=torch.float32)
+            check(LIB.mmt_spm_dq_sum(rows.data_ptr(), dq.data_ptr(), B, C, _stream()), "mmt_spm_dq_sum")
+        return dq, dkv, None, None
+
+
+class _HipBceLogits(torch.autograd.Function):
+    """weight * BCEWithLogitsLoss(logits, labels) (mean over the B logits; labels fp32 in [0, 1]) as a 0-dim
+    fp32 tensor: one launch each way (mmt_bce_logits / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight):
+        from ._lib import LIB, check
+        ctx.shape = logits.shape
+        logits = logits.detach().float().reshape(-1).contiguous()
+        labels = labels.detach().float().reshape(-1).contiguous()
+        if labels.shape != logits.shape:
+            raise ValueError("HIP bce_logits: one label per logit")
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        check(LIB.mmt_bce_logits(logits.data_ptr(), labels.data_ptr(), float(weight), loss.data_ptr(),
+                                 logits.numel(), _stream()), "mmt_bce_logits")
+        ctx.save_for_backward(logits, labels)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from ._lib import LIB, check
+        logits, labels = ctx.saved_tensors
+        dloss = dloss.float().contiguous()
+        dlogits = torch.empty_like(logits)
+        check(LIB.mmt_bce_logits_bwd(logits.data_ptr(), labels.data_ptr(), dloss.data_ptr(), ctx.weight,
+                                     dlogits.data_ptr(), logits.numel(), _stream()), "mmt_bce_logits_bwd")
+        return dlogits.view(ctx.shape), None, None
 
 
 class _HipAddUp(torch.autograd.Function):
@@ -1608,6 +1692,22 @@ class HipOps:
         out = _HipBoxLoss.apply(pred_cxcywh.view(-1, 4), gt_xywh, iou_weight, l1_weight)
         st = out.detach()
         return out[0], {"ciou": st[1], "l1": st[2], "iou": st[3]}
+
+    @staticmethod
+    def linear_cat(x, w0, b0, w1, b1, out_f32=False):
+        """Two Linears on the same rows as one GEMM, x [W0; W1]^T + [b0; b1] (_HipLinearCat)."""
+        return _HipLinearCat.apply(x, w0, b0, w1, b1, out_f32)
+
+    @staticmethod
+    def spm_attention(q, kv, heads, scale):
+        """The score decoder's single-query attention: q (B, C), or (1, C) shared by every batch row, kv
+        (B, Lk, 2C) = k | v, fp32 -> (B, C) fp32 (_HipSpmAttention)."""
+        return _HipSpmAttention.apply(q, kv, heads, scale)
+
+    @staticmethod
+    def bce_logits(logits, labels, weight=1.0):
+        """weight * BCEWithLogitsLoss(logits, labels), mean reduction (_HipBceLogits)."""
+        return _HipBceLogits.apply(logits, labels, weight)
 
     @staticmethod
     def msda_bimodal(value, offw, ref, hw):
@@ -2686,19 +2786,60 @@ def ce_center_mask(B, template_grid, device=None):
 
 
 # ----------------------------------------------------------------------------- score-head training
-def score_decoder_forward(sb, search_feat, template_feat, box_xyxy):
+def _score_decoder_tokens(sb, roi_tok, templ_tok, ops):
+    """ScoreDecoder.forward behind the PrRoIPool on `ops` (HipOps: libmmt_hip.so): roi_tok (b, 16, C) and
+    templ_tok (b, 2 nt1, C) fp32 memories -> logits (b,).  The forward stays in fp32 from end to end, as the
+    inference plan keeps this decoder in every runtime dtype (fp32 GEMMs on the master weights: the rows are few,
+    and with bf16 operands a handful of the score head's ReLU units land on the other side of zero, which alone
+    moves its gradients by ~10 %); the backward GEMMs take bf16 operands with fp32 accumulation (as autocast,
+    the box step's convention).  k and v of a memory are one [Wk; Wv] GEMM into the attention's k | v layout;
+    the score token is one row (M = 1), which layer 0's attention shares among the batch rows; the
+    score head's Linear(C, 1) runs zero-padded to 8 outputs (the GEMM's 16-byte granule) and column 0 is read."""
+    b, _, c = roi_tok.shape
+    lin_cat = getattr(ops, "linear_cat", None)
+    x = ops.layer_norm(sb.score_token.reshape(1, c), sb.norm1.weight, sb.norm1.bias, sb.norm1.eps, out_f32=True)
+    for i, mem in enumerate((roi_tok, templ_tok)):
+        q = ops.linear(x, sb.proj_q[i].weight, sb.proj_q[i].bias, out_f32=True)
+        m = mem.reshape(-1, c).float()
+        pk, pv = sb.proj_k[i], sb.proj_v[i]
+        if lin_cat is not None:
+            kv = lin_cat(m, pk.weight, pk.bias, pv.weight, pv.bias, out_f32=True)
+        else:
+            kv = torch.cat([ops.linear(m, pk.weight, pk.bias, out_f32=True),
+                            ops.linear(m, pv.weight, pv.bias, out_f32=True)], 1)
+        a = ops.spm_attention(q, kv.view(b, -1, 2 * c), sb.num_heads, sb.scale)
+        y = ops.linear(a, sb.proj[i].weight, sb.proj[i].bias, out_f32=True)
+        x = ops.layer_norm(y, sb.norm2[i].weight, sb.norm2[i].bias, sb.norm2[i].eps, out_f32=True)
+    n = len(sb.score_head.layers)
+    for i, layer in enumerate(sb.score_head.layers):
+        w, bias = layer.weight, layer.bias
+        pad = -w.shape[0] % 8
+        if pad:
+            w, bias = torch.cat([w, w.new_zeros(pad, w.shape[1])], 0), torch.cat([bias, bias.new_zeros(pad)], 0)
+        x = ops.linear(x, w, bias, out_f32=True)
+        if i < n - 1:
+            x = F.relu(x)
+    return x[:, :layer.weight.shape[0]].reshape(-1)
+
+
+def score_decoder_forward(sb, search_feat, template_feat, box_xyxy, ops=None):
     """ScoreDecoder.forward (lib/models/mixformer_cvt/score_decoder.py:32-66) with autograd; the ROI
     features come from PrRoIPool on libmmt_hip.so (mmt_amd.functional.prroi_pool2d, whose backward
     is mmt_prroi_pool_backward / _coor_backward).  search_feat (b,C,h,w) fp32, template_feat
-    (b,C,2*ht,wt), box_xyxy (b,4) normalised -> logits (b,)."""
+    (b,C,2*ht,wt), box_xyxy (b,4) normalised -> logits (b,).  ops None: eager PyTorch in fp32; an ops with
+    spm_attention (HipOps): everything behind the pooling on it (_score_decoder_tokens)."""
     from .functional import prroi_pool2d
     b, c, h, w = search_feat.shape
     H = sb.num_heads
     bb = (box_xyxy.clone() * w).view(-1, 4).float()
     rois = torch.cat([torch.arange(bb.shape[0], dtype=torch.float32, device=bb.device).view(-1, 1), bb], 1)
-    x = sb.norm1(sb.score_token.expand(b, -1, -1))
     roi = prroi_pool2d(search_feat.float().contiguous(), rois.contiguous(), sb.pool_size, sb.pool_size, 1.0)
     mem = [roi.flatten(2).transpose(1, 2), template_feat.float().flatten(2).transpose(1, 2)]
+    if ops is not None:
+        if not hasattr(ops, "spm_attention"):
+            raise ValueError("score_decoder_forward: ops without spm_attention")
+        return _score_decoder_tokens(sb, mem[0], mem[1], ops)
+    x = sb.norm1(sb.score_token.expand(b, -1, -1))
     for i in range(2):
         q = sb.proj_q[i](x).view(b, -1, H, c // H).transpose(1, 2)
         k = sb.proj_k[i](mem[i]).view(b, -1, H, c // H).transpose(1, 2)
@@ -2723,20 +2864,42 @@ class ScoreTrainStep:
     The frozen trunk (backbone, fusion, box head) runs on the HIP inference runtime `rt` (no
     autograd is needed through it); its search feature, template tokens and predicted boxes feed
     the score decoder, which runs with autograd.  The reference builds the ROI from the predicted
-    boxes (asymmetric_shared_online.py:398-413: forward_head is called without gt_bboxes)."""
+    boxes (asymmetric_shared_online.py:398-413: forward_head is called without gt_bboxes).
 
-    def __init__(self, net, rt, lr=1e-4, weight_decay=1e-4, grad_clip=0.1, score_weight=1.0):
-        self.net, self.rt = net, rt
+    ops None: the decoder as eager PyTorch in fp32, clip_grad_norm_ and torch.optim.AdamW.  ops=HipOps: the
+    decoder, the loss, the clip and AdamW on libmmt_hip.so (_score_decoder_tokens, HipOps.bce_logits,
+    mmt_amd.optim.HipAdamW), the trunk as the runtime's launch plan, and the whole step capturable as one
+    hipGraph (capture / replay)."""
+
+    def __init__(self, net, rt, lr=1e-4, weight_decay=1e-4, grad_clip=0.1, score_weight=1.0, ops=None):
+        self.net, self.rt, self.ops = net, rt, ops
         for n, p in net.named_parameters():
             p.requires_grad = "score" in n
         self.params = [p for n, p in net.named_parameters() if "score" in n]
-        self.opt = torch.optim.AdamW([{"params": self.params}], lr=lr, weight_decay=weight_decay)
         self.grad_clip, self.score_weight = grad_clip, score_weight
+        self._captured_hparams = None
+        if ops is not None:
+            # the decoder on `ops` (HipOps), clip + AdamW on mmt_amd.optim.HipAdamW, which also keeps the bf16
+            # copies of the decoder's Linear weights the GEMMs read; capturable (capture / replay)
+            from .optim import HipAdamW
+            if not hasattr(ops, "spm_attention") or not hasattr(ops, "bce_logits"):
+                raise ValueError("ScoreTrainStep: ops without spm_attention / bce_logits")
+            if rt.variant != "asym_online":
+                raise ValueError("ScoreTrainStep: only asym_online has a score branch")
+            shadow = [m.weight for m in net.score_branch.modules() if isinstance(m, torch.nn.Linear)]
+            self.opt = HipAdamW([{"params": self.params}], lr=lr, weight_decay=weight_decay, shadow=shadow,
+                                set_to_none=True)
+            return
+        self.opt = torch.optim.AdamW([{"params": self.params}], lr=lr, weight_decay=weight_decay)
         self.loss_fn = torch.nn.BCEWithLogitsLoss()
 
     @torch.no_grad()
     def trunk(self, t, o, s):
-        """-> search feature (B,C,gs,gs), template feature (B,C,2*gt,gt), boxes xyxy (B,4)."""
+        """-> search feature (B,C,gs,gs), template feature (B,C,2*gt,gt), boxes xyxy (B,4).
+        With ops: -> the decoder's two memories as token rows, RoI tokens (B,16,C) and template tokens
+        (B,2*nt1,C), fp32 (_trunk_tokens)."""
+        if self.ops is not None:
+            return self._trunk_tokens(t, o, s)
         rt, d = self.rt, self.rt.d
         box, _ = rt.forward(t, o, s, run_score_head=False)
         B = box.shape[0]
@@ -2748,8 +2911,32 @@ class ScoreTrainStep:
         xyxy = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
         return fused.clone(), templ.clone(), xyxy
 
+    def _trunk_tokens(self, t, o, s):
+        """The frozen trunk as the runtime's launch plan issued on the current stream (no nested graph replay, so
+        the step can be captured): the plan up to the corner read-out, which also writes the RoIs of the
+        predicted boxes, and the PrRoIPool of the inference score decoder, which writes the RoI tokens from the
+        channels-last fused map as rows (runtime._plan_spm).  The template memory is the first template's
+        rows of the fp32 token stream, RGB then TIR (one concatenating copy)."""
+        rt, d = self.rt, self.rt.d
+        B = t[0].shape[0]
+        ws = rt.workspace(B)
+        plan = ws.get("plan_score_train")
+        if plan is None:  # plan_score without the inference decoder behind its pooling
+            plan = ws["plan_score_train"] = [e for e in ws["plan_score"]
+                                             if not e[2].startswith("spm_") or e[2] == "spm_prroi"]
+        rt.load_inputs(ws, t, o, s)
+        rt.run_plan(plan)
+        X = ws["X"].view(2, B, d.ntok, d.C)[:, :, :d.nt1]
+        return ws["ROIT"].view(B, 16, d.C), torch.cat([X[0], X[1]], 1)
+
     def backward(self, t, o, s, labels):
         self.opt.zero_grad(set_to_none=True)
+        if self.ops is not None:
+            roi_tok, templ_tok = self.trunk(t, o, s)
+            scores = _score_decoder_tokens(self.net.score_branch, roi_tok, templ_tok, self.ops)
+            loss = self.ops.bce_logits(scores, labels, self.score_weight)
+            loss.backward()
+            return {"loss": loss.detach(), "scores": scores.detach()}
         fused, templ, xyxy = self.trunk(t, o, s)
         scores = score_decoder_forward(self.net.score_branch, fused, templ, xyxy)
         loss = self.loss_fn(scores, labels.float().view(-1)) * self.score_weight
@@ -2757,6 +2944,9 @@ class ScoreTrainStep:
         return {"loss": loss.detach(), "scores": scores.detach()}
 
     def apply(self):
+        if self.ops is not None:
+            self.opt.step(self.grad_clip)
+            return
         if self.grad_clip > 0:
             torch.nn.utils.clip_grad_norm_(self.params, self.grad_clip)
         self.opt.step()
@@ -2765,3 +2955,48 @@ class ScoreTrainStep:
         stats = self.backward(t, o, s, labels)
         self.apply()
         return stats
+
+    def _hparams(self):
+        return ([(g.get("lr"), g.get("weight_decay"), tuple(g.get("betas", ())), g.get("eps"))
+                 for g in self.opt.param_groups]
+                + [("grad_clip", self.grad_clip), ("score_weight", self.score_weight)])
+
+    def capture(self, t, o, s, labels, warmup=2):
+        """Record the whole step -- the trunk's launch plan, RoI pooling, decoder forward and backward, the loss,
+        clip + AdamW -- as one hipGraph on the static inputs t / o / s / labels (ops=HipOps only), as
+        TrainStep.capture does for the box step.  `warmup` eager steps run on a side stream first; they are real
+        steps.  The learning rate, weight decay, grad_clip and score_weight are those at capture time.
+        Returns the captured stats; replay() refreshes them."""
+        if self.ops is None:
+            raise RuntimeError("ScoreTrainStep.capture: the HIP step only (ops=HipOps)")
+        labels = labels.float().contiguous()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self(t, o, s, labels)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        self.opt.zero_grad(set_to_none=True)
+        with torch.cuda.graph(self.graph):
+            self.graph_stats = self(t, o, s, labels)
+        self.static_inputs = (t, o, s, labels)
+        self._captured_hparams = self._hparams()
+        return self.graph_stats
+
+    def replay(self, t=None, o=None, s=None, labels=None):
+        """One captured step; given inputs are first copied into the static ones (device copies).  The captured
+        launches carry the hyper-parameters of capture time as kernel arguments, so a changed learning rate,
+        weight decay, grad_clip or score_weight raises instead of replaying stale values: capture() again."""
+        if self._captured_hparams is None:
+            raise RuntimeError("ScoreTrainStep.replay: call capture() first")
+        if self._hparams() != self._captured_hparams:
+            raise RuntimeError("ScoreTrainStep.replay: hyper-parameters changed since capture (%s -> %s); call "
+                               "capture() again" % (self._captured_hparams, self._hparams()))
+        if t is not None:
+            st, so, ss, sl = self.static_inputs
+            for dst, src in zip(list(st) + list(so) + list(ss), list(t) + list(o) + list(s)):
+                dst.copy_(src)
+            sl.copy_(labels)
+        self.graph.replay()
+        return self.graph_stats
