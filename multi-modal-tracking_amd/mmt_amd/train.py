@@ -11,15 +11,18 @@ ltr_trainer.py (clip_grad_norm_ with TRAIN.GRAD_CLIP_NORM).
 
 What runs where.  The ViT backbones (≈ 85 % of the step's FLOPs) run on libmmt_hip.so through two
 autograd Functions: every Linear (patch embed as a GEMM on the unfolded patches, qkv, proj, fc1,
-fc2) forward and backward on the LDS-DMA bf16 GEMM (dX = dY W and dW = dY^T X after bf16
-transposes, fp32 accumulation, fp32 master weights), and the MAM attention forward (throughput
+fc2) forward and backward on the LDS-DMA bf16 GEMM (dX = dY W and dW = dY^T X on the operands as they
+are, read MN-major; bf16 transposed copies for dW only when the row count is no multiple of 8; fp32
+accumulation, fp32 master weights), and the MAM attention forward (throughput
 kernel, log-sum-exp kept) and backward (mmt_mam_attention_bwd).  The fusion encoder's Linears
 (value / offset / weight / output projections, FFN) take the same GEMM op, and its deformable
 sampling runs on mmt_ms_deform_attn_forward / _backward (mmt_amd.functional.MSDeformAttnFunction,
 the reference's MSDeformAttnFunction).  Clipping + AdamW is mmt_adamw_step (mmt_amd.optim.HipAdamW,
 three launches over every parameter, writing the bf16 copies of the backbone weights the GEMMs
 read).  The backbone LayerNorms run on mmt_layernorm / mmt_layernorm_bwd (_HipLayerNorm), and each
-block's MLP is one autograd Function whose GELU and GELU backward live in GEMM epilogues (_HipMlp); the
+block's MLP is one autograd Function whose GELU and GELU backward live in GEMM epilogues (_HipMlp).  The Linear
+Functions (_HipLinear, _HipLinearResidual, _HipMlp) are generic over the group count: one (weight, bias) set for
+one backbone or stream, two for the RGB / TIR backbones in lockstep on stacked rows (grouped GEMMs).  The
 fusion encoder's LayerNorms take the same kernels, and the fusion's adjust_* 1x1 convs + GroupNorms run on
 token rows as the HIP GEMM + mmt_groupnorm / mmt_groupnorm_bwd.  The residual adds and the corner head run as
 PyTorch-ROCm ops on the same
@@ -70,9 +73,6 @@ def _transpose(x, rows, cols, ld_out=None, ones_row=False):
     return out
 
 
-# The Linear backward reads dY, X and W as they are (MN-major GEMM operands, ds_read_b64_tr_b16) instead
-# of transposed copies; False: the transposing form (A/B knob, tools/train_ab.py)
-MN_MAJOR = True
 # The two-stream backbones in lockstep with grouped GEMMs (backbone_forward_pair); False: one after the
 # other (A/B knob, tools/train_ab.py)
 PAIR = True
@@ -80,30 +80,14 @@ _SPLITK = {}  # device -> (slab workspace, arrival tickets) of the dW GEMMs' spl
 
 
 def _splitk_ws(dev):
-    """The split-K workspace of the current stream (GEMMs on one stream run one after another, so one slab and one
-    ticket array per stream; the backward's side stream has its own)."""
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _SPLITK.get(key)
+    """The split-K workspace of a device: one slab and one ticket array, since all of a device's GEMMs are
+    stream-ordered (a step issues them on one stream, and a stream that takes over -- capture()'s warm-up and
+    capture streams -- waits for the one before it)."""
+    ws = _SPLITK.get(str(dev))
     if ws is None:
-        ws = _SPLITK[key] = (torch.empty(32 << 20, device=dev, dtype=torch.float32),
-                             torch.zeros(1 << 16, device=dev, dtype=torch.int32))
+        ws = _SPLITK[str(dev)] = (torch.empty(32 << 20, device=dev, dtype=torch.float32),
+                                  torch.zeros(1 << 16, device=dev, dtype=torch.int32))
     return ws
-
-
-# The pair backward's weight-gradient GEMMs on a side stream, beside the input-gradient GEMMs on the main stream
-# (round 6): the two are independent, so the second fills the CUs the first leaves idle in its last round of tiles
-# (the N = 768 GEMMs of the backbone run 1.55 rounds of 512 tile slots).  Measured no faster in an interleaved A/B
-# (tools/train_ab.py --only hip,single_stream: 569-576 dual vs 574-580 single samples/s, profiles/r06aa_train_ab.jsonl),
-# so off: an A/B knob.
-DUAL_STREAM = False
-_SIDE = {}
-
-
-def _side_stream(dev):
-    s = _SIDE.get(str(dev))
-    if s is None:
-        s = _SIDE[str(dev)] = torch.cuda.Stream(device=dev)
-    return s
 
 
 # Per-step GEMM accounting for bench.py's train_step.roofline: None, or a dict that every GEMM launch of the
@@ -190,63 +174,105 @@ def _bf16_weight(w):
     return w.detach().to(torch.bfloat16).contiguous()
 
 
+# -- Linear / Mlp autograd, generic over the group count G: G = 1 for one backbone or stream, G = 2 for the
+# two-stream backbones in lockstep: the RGB rows [0, M) and the TIR rows [M, 2M) of one stacked operand, each
+# modality with its own weights, as one grouped GEMM (groups 2) per Linear and per gradient.
+# One modality's dW GEMM (768-3080 output columns, K = the 8448 tokens of 16 pairs) is a 42-168 tile grid on
+# 256 CUs; the pair fills the chip twice as well (tools/dw_split_ab.py: 250-425 TFLOP/s at one group, 390-595
+# at two; the step 417 -> 462 samples/s, profiles/r04_train_pair_ab.jsonl).
+def _groups(t, G):
+    """The G row blocks of a stacked operand [G M][...] as _gemm's grouped form (views; None stays None)."""
+    return t if t is None else tuple(t.split(t.shape[0] // G))
+
+
 def _weight_grads(dy, x, M, N, K):
     """dW [N][K] and db [N] of y = x W^T + b from one GEMM: dy^T [x | 1] (a row of ones appended to the
     transposed activations gives the bias gradient as output column K; fp32 accumulation).  The GEMM
     writes dW contiguous and the bias column alone as a contiguous [N] vector behind it (c2_copy 4), so
     autograd takes both as the parameters' .grad as they are (round 5: a strided db column was cloned by
-    AccumulateGrad, ~100 small copy launches per training step)."""
-    buf = torch.empty(N * (K + 1), device=dy.device, dtype=torch.float32)
-    dw, db = buf[:N * K].view(N, K), buf[N * K:]
-    if MN_MAJOR and M % 8 == 0:  # dY [M][N] and X [M][K] read as they are (a_t, w_t 2: the ones column)
-        _gemm(dy, x, N, K + 8, M, out_f32=True, c=dw, ldc=K, c2=db, c2_copy=4, a_t=1, w_t=2, ldw=K, lda=N,
+    AccumulateGrad, ~100 small copy launches per training step).
+    dy [M][N] and x [M][K] tensors -> (dW, db); G-tuples of them -> [(dW, db) per group], from one grouped
+    launch when M % 8 == 0."""
+    grouped = isinstance(dy, tuple)
+    dys, xs = (dy, x) if grouped else ((dy,), (x,))
+    bufs = [torch.empty(N * (K + 1), device=dys[0].device, dtype=torch.float32) for _ in dys]
+    dws = tuple(b[:N * K].view(N, K) for b in bufs)
+    dbs = tuple(b[N * K:] for b in bufs)
+    if M % 8 == 0:  # dY [M][N] and X [M][K] read as they are (MN-major operands; a_t, w_t 2: the ones column)
+        _gemm(dys, xs, N, K + 8, M, out_f32=True, c=dws, ldc=K, c2=dbs, c2_copy=4, a_t=1, w_t=2, ldw=K, lda=N,
               splitk=True)
-        return dw, db
-    Mp = (M + 7) // 8 * 8  # contraction over tokens, zero-padded to the GEMM's K granule
-    _gemm(_transpose(dy, M, N, Mp), _transpose(x, M, K, Mp, ones_row=True), N, K + 8, Mp, out_f32=True,
-          c=dw, ldc=K, c2=db, c2_copy=4)
-    return dw, db
+    else:  # transposed copies, the contraction over tokens zero-padded to the GEMM's K granule
+        Mp = (M + 7) // 8 * 8
+        for u, v, dw, db in zip(dys, xs, dws, dbs):
+            _gemm(_transpose(u, M, N, Mp), _transpose(v, M, K, Mp, ones_row=True), N, K + 8, Mp, out_f32=True,
+                  c=dw, ldc=K, c2=db, c2_copy=4)
+    out = list(zip(dws, dbs))
+    return out if grouped else out[0]
 
 
-def _dx(dy, wb, M, N, K, act=0, r=None):
-    """dX [M][K] = dY [M][N] W [N][K] (bf16 out; act 5: times GELU'(r))."""
-    if MN_MAJOR:  # W read MN-major as it is
-        return _gemm(dy, wb, M, K, N, act=act, r=r, w_t=1, ldw=K)
-    return _gemm(dy, _transpose(wb, N, K), M, K, N, act=act, r=r)
+def _dx(dy, wb, M, N, K, act=0, r=None, out_f32=False):
+    """dX [M][K] = dY [M][N] W [N][K], W read MN-major as it is (bf16 out, fp32 with out_f32; act 5: times
+    GELU'(r); an fp32 r is added).  Tensors, or G-tuples for one grouped launch -> [G M][K]."""
+    return _gemm(dy, wb, M, K, N, act=act, r=r, out_f32=out_f32, w_t=1, ldw=K)
+
+
+def _linear_grads(dy, x, wbs, M, N, K, need_dx, act=0, r=None):
+    """The backward of y = x W_g^T + b_g on stacked dy [G M][N] / x [G M][K] (wbs: the G bf16 weights):
+    (dX [G M][K] or None, [(dW, db) per group]).  One group issues its dX GEMM first, the pair its dW GEMM: the
+    order each had as a Function of its own, kept so that a training step's launch sequence stays what it was."""
+    G = len(wbs)
+    dys = _groups(dy, G)
+    if G == 1:
+        dx = _dx(dys, wbs, M, N, K, act, _groups(r, G)) if need_dx else None
+        return dx, _weight_grads(dys, _groups(x, G), M, N, K)
+    grads = _weight_grads(dys, _groups(x, G), M, N, K)
+    return (_dx(dys, wbs, M, N, K, act, _groups(r, G)) if need_dx else None), grads
+
+
+def _linear_fwd(ctx, x, wbs, bs, out_f32, w32=None):
+    """y = x W_g^T + b_g on stacked x [G M][K] bf16 (wbs / bs: the G bf16 weights [N][K] and fp32 biases); an
+    fp32 x (G = 1, the score decoder) runs as an fp32 GEMM on the master weight w32, y fp32.  Saves bf16(x) and
+    wbs for _linear_bwd."""
+    G = len(wbs)
+    M, K = x.shape[0] // G, x.shape[1]
+    N = wbs[0].shape[0]
+    if x.dtype == torch.float32:
+        y = _gemm(x, w32, M, N, K, bias=bs[0], out_f32=True, f32=True)
+        x = x.to(torch.bfloat16)
+    else:
+        y = _gemm(_groups(x, G), wbs, M, N, K, bias=bs, out_f32=out_f32)
+    ctx.save_for_backward(x, *wbs)
+    return y
+
+
+def _linear_bwd(ctx, dy, need_dx):
+    x, *wbs = ctx.saved_tensors
+    G = len(wbs)
+    return _linear_grads(dy.to(torch.bfloat16).contiguous(), x, wbs, x.shape[0] // G, wbs[0].shape[0], x.shape[1],
+                         need_dx)
 
 
 class _HipLinear(torch.autograd.Function):
-    """y = x W^T + b (nn.Linear) with bf16 operands; x [M][K] bf16, W [N][K] fp32 master, b [N]; y bf16,
+    """y = x W^T + b (nn.Linear) with bf16 operands; x [M][K] bf16, params (W [N][K] fp32 master, b [N]); y bf16,
     or fp32 straight from the GEMM's accumulators (out_f32: the residual-stream adds, no cast pass).
     An fp32 x (the score decoder, which the inference plan too keeps in fp32) runs the forward as an fp32 GEMM on
-    the master weight, y fp32; the backward is the same either way, on bf16(x) and the bf16 weight."""
+    the master weight, y fp32; the backward is the same either way, on bf16(x) and the bf16 weight.
+    Two (W, b) pairs: the two modalities, x [2M][K] with the RGB rows first, grouped GEMMs."""
 
     @staticmethod
-    def forward(ctx, x, w, b, out_f32=False):
-        M, K = x.shape
-        N = w.shape[0]
+    def forward(ctx, x, out_f32, *params):
+        ws, bs = params[0::2], params[1::2]
         x = x.contiguous()
-        wb = _bf16_weight(w)  # bf16 shadow written by HipAdamW's update (same values)
-        if x.dtype == torch.float32:
-            y = _gemm(x, w.detach().contiguous(), M, N, K, bias=b.detach().float().contiguous(), out_f32=True,
-                      f32=True)
-            ctx.save_for_backward(x.to(torch.bfloat16), wb)
-            return y
-        y = _gemm(x, wb, M, N, K, bias=b.detach().float().contiguous(), out_f32=out_f32)
-        ctx.save_for_backward(x, wb)
-        return y
+        wbs = tuple(_bf16_weight(w) for w in ws)  # bf16 shadows written by HipAdamW's update (same values)
+        w32 = ws[0].detach().contiguous() if x.dtype == torch.float32 else None
+        return _linear_fwd(ctx, x, wbs, tuple(b.detach() for b in bs), out_f32, w32)
 
     @staticmethod
     def backward(ctx, dy):
-        x, wb = ctx.saved_tensors
-        M, K = x.shape
-        N = wb.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
-        dx = _dx(dy, wb, M, N, K) if ctx.needs_input_grad[0] else None
         # dW and the bias gradient from one GEMM: x^T carries an extra row of ones, so output column
         # K of dy^T [x | 1] is sum_m dy[m][n] (the same bf16 dy, fp32 accumulation; no reduce kernel)
-        dw, db = _weight_grads(dy, x, M, N, K)
-        return dx, dw, db, None
+        dx, grads = _linear_bwd(ctx, dy, ctx.needs_input_grad[0])
+        return (dx, None, *(t for dwb in grads for t in dwb))
 
 
 class _HipLinearDup(torch.autograd.Function):
@@ -258,55 +284,15 @@ class _HipLinearDup(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, out_f32=False):
-        M, K2 = x.shape
-        N = w.shape[0]
         x = x.contiguous()
         wb = _bf16_weight(w)
-        wb = torch.cat([wb, wb], 1)
-        y = _gemm(x, wb, M, N, K2, bias=b.detach().float().contiguous(), out_f32=out_f32)
-        ctx.save_for_backward(x, wb)
-        return y
+        return _linear_fwd(ctx, x, (torch.cat([wb, wb], 1),), (b.detach(),), out_f32)
 
     @staticmethod
     def backward(ctx, dy):
-        x, wb = ctx.saved_tensors
-        M, K2 = x.shape
-        N = wb.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
-        dx = _dx(dy, wb, M, N, K2) if ctx.needs_input_grad[0] else None
-        dw, db = _weight_grads(dy, x, M, N, K2)
-        return dx, dw[:, :K2 // 2] + dw[:, K2 // 2:], db, None
-
-
-class _HipMlp(torch.autograd.Function):
-    """timm Mlp of the ViT blocks (mixformer.py:136-139): y = fc2(GELU(fc1(x))) with x [M][C] bf16, y [M][C]
-    fp32 (the residual branch).  fc1 runs with the GELU epilogue and also stores its pre-activation (bf16,
-    c2_copy 2); the backward's dX GEMM of fc2 multiplies by GELU'(pre-activation) in its epilogue (act 5),
-    so neither the activation nor its gradient is a separate pass."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2):
-        M, C = x.shape
-        F4 = w1.shape[0]
-        x = x.contiguous()
-        wb1, wb2 = _bf16_weight(w1), _bf16_weight(w2)
-        hp = torch.empty(M, F4, device=x.device, dtype=torch.bfloat16)
-        h = _gemm(x, wb1, M, F4, C, bias=b1.detach(), act=1, c2=hp, c2_copy=2)
-        y = _gemm(h, wb2, M, C, F4, bias=b2.detach(), out_f32=True)
-        ctx.save_for_backward(x, wb1, wb2, h, hp)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, wb1, wb2, h, hp = ctx.saved_tensors
-        M, C = x.shape
-        F4 = wb1.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
-        dhp = _dx(dy, wb2, M, C, F4, act=5, r=hp)  # d(pre-activation), bf16
-        dw2, db2 = _weight_grads(dy, h, M, C, F4)
-        dx = _dx(dhp, wb1, M, F4, C) if ctx.needs_input_grad[0] else None
-        dw1, db1 = _weight_grads(dhp, x, M, F4, C)
-        return dx, dw1, db1, dw2, db2
+        dx, ((dw, db),) = _linear_bwd(ctx, dy, ctx.needs_input_grad[0])
+        K = dw.shape[1] // 2
+        return dx, dw[:, :K] + dw[:, K:], db, None
 
 
 def _scaled_bf16(dy, keep, rows_per):
@@ -322,231 +308,90 @@ def _scaled_bf16(dy, keep, rows_per):
     return out
 
 
-class _HipLinearResidual(torch.autograd.Function):
-    """x + keep * (a W^T + b) in one GEMM (fp32 residual stream x [M][N] as the epilogue's R, keep [B] the
-    per-sample stochastic-depth scale over blocks of M / B rows as its row_scale, or None): the block's
-    proj + DropPath + residual add (mixformer.py:136-137) without the addcmul pass; the backward hands
-    the stream gradient through and scales + casts the branch gradient in one pass."""
-
-    @staticmethod
-    def forward(ctx, x, a, w, b, keep):
-        M, K = a.shape
-        N = w.shape[0]
-        a = a.contiguous()
-        wb = _bf16_weight(w)
-        rows = M // keep.shape[0] if keep is not None else 1
-        y = _gemm(a, wb, M, N, K, bias=b.detach(), out_f32=True, r=x.detach().reshape(M, N),
-                  row_scale=keep, row_scale_div=rows)
-        ctx.save_for_backward(a, wb, keep)
-        ctx.rows = rows
-        return y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        a, wb, keep = ctx.saved_tensors
-        M, K = a.shape
-        N = wb.shape[0]
-        dy = _scaled_bf16(dout.reshape(M, N), keep, ctx.rows)
-        da = _dx(dy, wb, M, N, K) if ctx.needs_input_grad[1] else None
-        dw, db = _weight_grads(dy, a, M, N, K)
-        return dout, da, dw, db, None
-
-
-class _HipMlpResidual(torch.autograd.Function):
-    """x + keep * fc2(GELU(fc1(xn))) (the block's MLP branch + DropPath + residual, mixformer.py:138-139):
-    _HipMlp with the residual add and the per-sample scale in fc2's epilogue."""
-
-    @staticmethod
-    def forward(ctx, x, xn, w1, b1, w2, b2, keep):
-        M, C = xn.shape
-        F4 = w1.shape[0]
-        xn = xn.contiguous()
-        wb1, wb2 = _bf16_weight(w1), _bf16_weight(w2)
-        rows = M // keep.shape[0] if keep is not None else 1
-        hp = torch.empty(M, F4, device=xn.device, dtype=torch.bfloat16)
-        h = _gemm(xn, wb1, M, F4, C, bias=b1.detach(), act=1, c2=hp, c2_copy=2)
-        y = _gemm(h, wb2, M, C, F4, bias=b2.detach(), out_f32=True, r=x.detach().reshape(M, C), row_scale=keep,
-                  row_scale_div=rows)
-        ctx.save_for_backward(xn, wb1, wb2, h, hp, keep)
-        ctx.rows = rows
-        return y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        xn, wb1, wb2, h, hp, keep = ctx.saved_tensors
-        M, C = xn.shape
-        F4 = wb1.shape[0]
-        dy = _scaled_bf16(dout.reshape(M, C), keep, ctx.rows)
-        dhp = _dx(dy, wb2, M, C, F4, act=5, r=hp)
-        dw2, db2 = _weight_grads(dy, h, M, C, F4)
-        dxn = _dx(dhp, wb1, M, F4, C) if ctx.needs_input_grad[1] else None
-        dw1, db1 = _weight_grads(dhp, xn, M, F4, C)
-        return dout, dxn, dw1, db1, dw2, db2, None
-
-
-# -- the two-stream backbones in lockstep: the RGB rows [0, M) and the TIR rows [M, 2M) of one stacked
-# operand, each modality with its own weights, as one grouped GEMM (groups 2) per Linear and per gradient.
-# One modality's dW GEMM (768-3080 output columns, K = the 8448 tokens of 16 pairs) is a 42-168 tile grid on
-# 256 CUs; the pair fills the chip twice as well (tools/dw_split_ab.py: 250-425 TFLOP/s at one group, 390-595
-# at two; the step 417 -> 462 samples/s, profiles/r04_train_pair_ab.jsonl).
-class _Beside:
-    """Runs work on the device's side stream beside the calling (main) stream: run(fn, ...) makes the side stream
-    wait for everything issued on the main stream so far, then issues fn there; leaving the block makes the main
-    stream wait for the side stream.  Every tensor the side work reads or writes must be allocated on the main
-    stream and stay referenced until the block ends (so no block is recycled while the side stream uses it).
-    Captured in a hipGraph as a fork / join.  With DUAL_STREAM False (or on the host) run() calls fn inline."""
-
-    def __init__(self, dev):
-        self.on = DUAL_STREAM and MN_MAJOR and torch.device(dev).type == "cuda"
-        self.dev = dev
-
-    def __enter__(self):
-        if self.on:
-            self.main, self.side = torch.cuda.current_stream(self.dev), _side_stream(self.dev)
-        return self
-
-    def run(self, fn, *a, **kw):
-        if not self.on:
-            return fn(*a, **kw)
-        self.side.wait_stream(self.main)
-        with torch.cuda.stream(self.side):
-            return fn(*a, **kw)
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.main.wait_stream(self.side)
-        return False
-
-
-def _halves(t, M):
-    return t[:M], t[M:]
-
-
-def _wg2_bufs(dev, N, K):
-    """The two modalities' [dW | db] buffers of _weight_grads2 (allocated on the calling stream)."""
-    return [torch.empty(N * (K + 1), device=dev, dtype=torch.float32) for _ in range(2)]
-
-
-def _weight_grads2(dy, x, M, N, K, bufs=None):
-    """_weight_grads of both modalities (dy [2M][N], x [2M][K]) in one launch: ((dW, db) RGB, (dW, db) TIR).
-    bufs: preallocated _wg2_bufs (the dual-stream backward allocates on the main stream)."""
-    bufs = bufs if bufs is not None else _wg2_bufs(dy.device, N, K)
-    dws = tuple(b[:N * K].view(N, K) for b in bufs)
-    dbs = tuple(b[N * K:] for b in bufs)
-    if not (MN_MAJOR and M % 8 == 0):
-        return [_weight_grads(u, v, M, N, K) for u, v in zip(_halves(dy, M), _halves(x, M))]
-    _gemm(_halves(dy, M), _halves(x, M), N, K + 8, M, out_f32=True, c=dws, ldc=K, c2=dbs, c2_copy=4, a_t=1,
-          w_t=2, ldw=K, lda=N, splitk=True)
-    return [(dws[0], dbs[0]), (dws[1], dbs[1])]
-
-
-def _dx2(dy, wbs, M, N, K, act=0, r=None):
-    """_dx of both modalities: dX [2M][K] = dY [2M][N] W_m [N][K] per half (bf16; act 5 with r [2M][N])."""
-    rr = _halves(r, M) if r is not None else None
-    if MN_MAJOR:
-        return _gemm(_halves(dy, M), wbs, M, K, N, act=act, r=rr, w_t=1, ldw=K)
-    return _gemm(_halves(dy, M), tuple(_transpose(w, N, K) for w in wbs), M, K, N, act=act, r=rr)
-
-
-class _HipLinear2(torch.autograd.Function):
-    """_HipLinear for the two modalities: x [2M][K] bf16 (RGB rows first), weights (w0, b0) / (w1, b1)."""
-
-    @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1, out_f32=False):
-        M2, K = x.shape
-        M, N = M2 // 2, w0.shape[0]
-        x = x.contiguous()
-        wbs = (_bf16_weight(w0), _bf16_weight(w1))
-        y = _gemm(_halves(x, M), wbs, M, N, K, bias=(b0.detach().float(), b1.detach().float()), out_f32=out_f32)
-        ctx.save_for_backward(x, *wbs)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, wb0, wb1 = ctx.saved_tensors
-        M2, K = x.shape
-        M, N = M2 // 2, wb0.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
-        with _Beside(dy.device) as side:
-            (dw0, db0), (dw1, db1) = side.run(_weight_grads2, dy, x, M, N, K, bufs=_wg2_bufs(dy.device, N, K))
-            dx = _dx2(dy, (wb0, wb1), M, N, K) if ctx.needs_input_grad[0] else None
-        return dx, dw0, db0, dw1, db1, None
-
-
-def _residual_gemm2(a, wbs, bs, x, keep, M, N, K, rows):
-    """x + keep * (a W_m^T + b_m) for both halves, fp32 [2M][N]: one grouped launch without stochastic depth;
-    with it one launch per modality (the row scale is one vector indexed by the row within a group; a
-    per-group index and so one launch measured no faster: 458.6 vs 462.1 samples/s on the step)."""
-    xr = x.detach().reshape(2 * M, N)
-    if keep is None:
-        return _gemm(_halves(a, M), wbs, M, N, K, bias=bs, out_f32=True, r=_halves(xr, M))
-    y = torch.empty(2 * M, N, device=a.device, dtype=torch.float32)
-    B = keep.shape[0] // 2
-    for m, (am, ym, xm) in enumerate(zip(_halves(a, M), _halves(y, M), _halves(xr, M))):
-        _gemm(am, wbs[m], M, N, K, bias=bs[m], out_f32=True, r=xm, c=ym, row_scale=keep[m * B:(m + 1) * B],
+def _residual_gemm(a, wbs, bs, x, keep, M, N, K):
+    """x + keep * (a W_g^T + b_g) on stacked a [G M][K], fp32 [G M][N] (x the fp32 residual stream as the
+    epilogue's R, keep [G B] the per-sample stochastic-depth scale over blocks of M / B rows as its row_scale;
+    either may be None): one launch, except for the pair under stochastic depth, which takes one launch per
+    modality (the row scale is one vector indexed by the row within a group; a per-group index and so one
+    launch measured no faster: 458.6 vs 462.1 samples/s on the step).  -> (y, rows per keep entry)."""
+    G = len(wbs)
+    xr = x.detach().reshape(G * M, N) if x is not None else None
+    rows = G * M // keep.shape[0] if keep is not None else 1
+    if keep is None or G == 1:
+        return _gemm(_groups(a, G), wbs, M, N, K, bias=bs, out_f32=True, r=_groups(xr, G), row_scale=keep,
+                     row_scale_div=rows), rows
+    y = torch.empty(G * M, N, device=a.device, dtype=torch.float32)
+    B = keep.shape[0] // G
+    for g, (ag, yg, xg) in enumerate(zip(_groups(a, G), _groups(y, G), _groups(xr, G))):
+        _gemm(ag, wbs[g], M, N, K, bias=bs[g], out_f32=True, r=xg, c=yg, row_scale=keep[g * B:(g + 1) * B],
               row_scale_div=rows)
-    return y
+    return y, rows
 
 
-class _HipLinearResidual2(torch.autograd.Function):
-    """_HipLinearResidual for the two modalities: x [2B][ntok][N] fp32, a [2M][K], keep [2B] or None."""
+class _HipLinearResidual(torch.autograd.Function):
+    """x + keep * (a W^T + b) in one GEMM (_residual_gemm; x [B][ntok][N] fp32, a [M][K] bf16, keep [B] or None):
+    the block's proj + DropPath + residual add (mixformer.py:136-137) without the addcmul pass; the backward hands
+    the stream gradient through and scales + casts the branch gradient in one pass.  Two (W, b) pairs: the two
+    modalities, x [2B][ntok][N], a [2M][K], keep [2B]."""
 
     @staticmethod
-    def forward(ctx, x, a, w0, b0, w1, b1, keep):
-        M2, K = a.shape
-        M, N = M2 // 2, w0.shape[0]
+    def forward(ctx, x, a, keep, *params):
+        ws, bs = params[0::2], params[1::2]
+        G = len(ws)
+        M, K = a.shape[0] // G, a.shape[1]
         a = a.contiguous()
-        wbs = (_bf16_weight(w0), _bf16_weight(w1))
-        rows = M2 // keep.shape[0] if keep is not None else 1
-        y = _residual_gemm2(a, wbs, (b0.detach(), b1.detach()), x, keep, M, N, K, rows)
-        ctx.save_for_backward(a, *wbs, keep)
-        ctx.rows = rows
+        wbs = tuple(_bf16_weight(w) for w in ws)
+        y, ctx.rows = _residual_gemm(a, wbs, tuple(b.detach() for b in bs), x, keep, M, ws[0].shape[0], K)
+        ctx.save_for_backward(a, keep, *wbs)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dout):
-        a, wb0, wb1, keep = ctx.saved_tensors
-        M2, K = a.shape
-        M, N = M2 // 2, wb0.shape[0]
-        dy = _scaled_bf16(dout.reshape(M2, N), keep, ctx.rows)
-        with _Beside(dy.device) as side:
-            (dw0, db0), (dw1, db1) = side.run(_weight_grads2, dy, a, M, N, K, bufs=_wg2_bufs(dy.device, N, K))
-            da = _dx2(dy, (wb0, wb1), M, N, K) if ctx.needs_input_grad[1] else None
-        return dout, da, dw0, db0, dw1, db1, None
+        a, keep, *wbs = ctx.saved_tensors
+        G = len(wbs)
+        M, K = a.shape[0] // G, a.shape[1]
+        N = wbs[0].shape[0]
+        dy = _scaled_bf16(dout.reshape(G * M, N), keep, ctx.rows)
+        da, grads = _linear_grads(dy, a, wbs, M, N, K, ctx.needs_input_grad[1])
+        return (dout, da, None, *(t for dwb in grads for t in dwb))
 
 
-class _HipMlpResidual2(torch.autograd.Function):
-    """_HipMlpResidual for the two modalities: fc1 (GELU epilogue, pre-activation stored) as one grouped GEMM,
-    fc2 + DropPath + residual as _residual_gemm2, the backward's four GEMMs grouped."""
+class _HipMlp(torch.autograd.Function):
+    """timm Mlp of the ViT blocks (mixformer.py:136-139): y = fc2(GELU(fc1(xn))) with xn [M][C] bf16, y [M][C]
+    fp32 (the residual branch); params (W1, b1, W2, b2).  fc1 runs with the GELU epilogue and also stores its
+    pre-activation (bf16, c2_copy 2); the backward's dX GEMM of fc2 multiplies by GELU'(pre-activation) in its
+    epilogue (act 5), so neither the activation nor its gradient is a separate pass.
+    With x [B][ntok][C] fp32: x + keep * Mlp(xn) (the block's MLP branch + DropPath + residual, mixformer.py:
+    138-139), the residual add and the per-sample scale in fc2's epilogue (_residual_gemm).  Two parameter sets:
+    the two modalities, xn [2M][C], every GEMM grouped."""
 
     @staticmethod
-    def forward(ctx, x, xn, w10, b10, w20, b20, w11, b11, w21, b21, keep):
-        M2, C = xn.shape
-        M, F4 = M2 // 2, w10.shape[0]
+    def forward(ctx, x, xn, keep, *params):
+        G = len(params) // 4
+        M, C = xn.shape[0] // G, xn.shape[1]
+        F4 = params[0].shape[0]
         xn = xn.contiguous()
-        wb1 = (_bf16_weight(w10), _bf16_weight(w11))
-        wb2 = (_bf16_weight(w20), _bf16_weight(w21))
-        rows = M2 // keep.shape[0] if keep is not None else 1
-        hp = torch.empty(M2, F4, device=xn.device, dtype=torch.bfloat16)
-        h = _gemm(_halves(xn, M), wb1, M, F4, C, bias=(b10.detach(), b11.detach()), act=1, c2=_halves(hp, M),
-                  c2_copy=2)
-        y = _residual_gemm2(h, wb2, (b20.detach(), b21.detach()), x, keep, M, C, F4, rows)
-        ctx.save_for_backward(xn, *wb1, *wb2, h, hp, keep)
-        ctx.rows = rows
-        return y.view(x.shape)
+        wb1 = tuple(_bf16_weight(w) for w in params[0::4])
+        wb2 = tuple(_bf16_weight(w) for w in params[2::4])
+        b1, b2 = tuple(b.detach() for b in params[1::4]), tuple(b.detach() for b in params[3::4])
+        hp = torch.empty(G * M, F4, device=xn.device, dtype=torch.bfloat16)
+        h = _gemm(_groups(xn, G), wb1, M, F4, C, bias=b1, act=1, c2=_groups(hp, G), c2_copy=2)
+        y, ctx.rows = _residual_gemm(h, wb2, b2, x, keep, M, C, F4)
+        ctx.save_for_backward(xn, h, hp, keep, *wb1, *wb2)
+        return y if x is None else y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dout):
-        xn, wb10, wb11, wb20, wb21, h, hp, keep = ctx.saved_tensors
-        M2, C = xn.shape
-        M, F4 = M2 // 2, wb10.shape[0]
-        dy = _scaled_bf16(dout.reshape(M2, C), keep, ctx.rows)
-        with _Beside(dy.device) as side:
-            (dw20, db20), (dw21, db21) = side.run(_weight_grads2, dy, h, M, C, F4, bufs=_wg2_bufs(dy.device, C, F4))
-            dhp = _dx2(dy, (wb20, wb21), M, C, F4, act=5, r=hp)
-            (dw10, db10), (dw11, db11) = side.run(_weight_grads2, dhp, xn, M, F4, C, bufs=_wg2_bufs(dy.device, F4, C))
-            dxn = _dx2(dhp, (wb10, wb11), M, F4, C) if ctx.needs_input_grad[1] else None
-        return dout, dxn, dw10, db10, dw20, db20, dw11, db11, dw21, db21, None
+        xn, h, hp, keep, *wbs = ctx.saved_tensors
+        G = len(wbs) // 2
+        wb1, wb2 = wbs[:G], wbs[G:]
+        M, C = xn.shape[0] // G, xn.shape[1]
+        F4 = wb1[0].shape[0]
+        dy = _scaled_bf16(dout.reshape(G * M, C), keep, ctx.rows)
+        dhp, g2 = _linear_grads(dy, h, wb2, M, C, F4, True, act=5, r=hp)  # d(pre-activation), bf16
+        dxn, g1 = _linear_grads(dhp, xn, wb1, M, F4, C, ctx.needs_input_grad[1])
+        return (dout if ctx.needs_input_grad[0] else None, dxn, None,
+                *(t for dwb1, dwb2 in zip(g1, g2) for t in (*dwb1, *dwb2)))
 
 
 class _HipMamAttention(torch.autograd.Function):
@@ -1279,10 +1124,7 @@ class _HipEncoderFFN(torch.autograd.Function):
         dw1, db1 = _weight_grads(dh, xb, M, F_, d)
         dx = None
         if ctx.needs_input_grad[0]:  # dX = dh W1 + the stream gradient (fp32 epilogue residual)
-            if MN_MAJOR:
-                dx = _gemm(dh, wb1, M, d, F_, r=dout, out_f32=True, w_t=1, ldw=d)
-            else:
-                dx = _gemm(dh, _transpose(wb1, F_, d), M, d, F_, r=dout, out_f32=True)
+            dx = _dx(dh, wb1, M, F_, d, r=dout, out_f32=True)
         return dx, dw1, db1, dw2, db2, None, None, None
 
 
@@ -1294,29 +1136,17 @@ class _HipLinearCat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, b0, w1, b1, out_f32=False):
-        M, K = x.shape
-        N0, N1 = w0.shape[0], w1.shape[0]
         x = x.contiguous()
         wb = torch.cat([_bf16_weight(w0), _bf16_weight(w1)], 0)
-        bias = torch.cat([b0.detach().float(), b1.detach().float()], 0)
-        if x.dtype == torch.float32:  # fp32 forward on the master weights, as _HipLinear's
-            y = _gemm(x, torch.cat([w0.detach(), w1.detach()], 0), M, N0 + N1, K, bias=bias, out_f32=True, f32=True)
-            ctx.save_for_backward(x.to(torch.bfloat16), wb)
-            ctx.n0 = N0
-            return y
-        y = _gemm(x, wb, M, N0 + N1, K, bias=bias, out_f32=out_f32)
-        ctx.save_for_backward(x, wb)
-        ctx.n0 = N0
-        return y
+        bias = torch.cat([b0.detach(), b1.detach()], 0)
+        # an fp32 x: the forward on the master weights, as _HipLinear's
+        w32 = torch.cat([w0.detach(), w1.detach()], 0) if x.dtype == torch.float32 else None
+        ctx.n0 = w0.shape[0]
+        return _linear_fwd(ctx, x, (wb,), (bias,), out_f32, w32)
 
     @staticmethod
     def backward(ctx, dy):
-        x, wb = ctx.saved_tensors
-        M, K = x.shape
-        N = wb.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
-        dx = _dx(dy, wb, M, N, K) if ctx.needs_input_grad[0] else None
-        dw, db = _weight_grads(dy, x, M, N, K)
+        dx, ((dw, db),) = _linear_bwd(ctx, dy, ctx.needs_input_grad[0])
         n0 = ctx.n0
         return dx, dw[:n0], db[:n0], dw[n0:], db[n0:], None
 
@@ -1553,7 +1383,7 @@ class HipOps:
 
     @staticmethod
     def linear(x, weight, bias, out_f32=False):
-        return _HipLinear.apply(x, weight, bias, out_f32)
+        return _HipLinear.apply(x, out_f32, weight, bias)
 
     @staticmethod
     def linear_dup(x, weight, bias, out_f32=False):
@@ -1568,32 +1398,32 @@ class HipOps:
     @staticmethod
     def mlp(x, w1, b1, w2, b2):
         """fc2(GELU(fc1(x))), x [M][C] bf16 -> fp32 (_HipMlp)."""
-        return _HipMlp.apply(x, w1, b1, w2, b2)
+        return _HipMlp.apply(None, x, None, w1, b1, w2, b2)
 
     @staticmethod
     def linear_residual(x, a, weight, bias, keep):
         """x + keep * Linear(a) (fp32 x, bf16 a, keep [B] per-sample scale or None) (_HipLinearResidual)."""
-        return _HipLinearResidual.apply(x, a, weight, bias, keep)
+        return _HipLinearResidual.apply(x, a, keep, weight, bias)
 
     @staticmethod
     def mlp_residual(x, xn, w1, b1, w2, b2, keep):
-        """x + keep * Mlp(xn) (_HipMlpResidual)."""
-        return _HipMlpResidual.apply(x, xn, w1, b1, w2, b2, keep)
+        """x + keep * Mlp(xn) (_HipMlp with its residual epilogue)."""
+        return _HipMlp.apply(x, xn, keep, w1, b1, w2, b2)
 
     @staticmethod
     def linear2(x, w0, b0, w1, b1, out_f32=False):
-        """Linear of the stacked modalities, rows [0, M) with (w0, b0) and [M, 2M) with (w1, b1) (_HipLinear2)."""
-        return _HipLinear2.apply(x, w0, b0, w1, b1, out_f32)
+        """Linear of the stacked modalities, rows [0, M) with (w0, b0) and [M, 2M) with (w1, b1) (_HipLinear, two groups)."""
+        return _HipLinear.apply(x, out_f32, w0, b0, w1, b1)
 
     @staticmethod
     def linear_residual2(x, a, w0, b0, w1, b1, keep):
-        """linear_residual of the stacked modalities (_HipLinearResidual2; keep [2B] or None)."""
-        return _HipLinearResidual2.apply(x, a, w0, b0, w1, b1, keep)
+        """linear_residual of the stacked modalities (_HipLinearResidual, two groups; keep [2B] or None)."""
+        return _HipLinearResidual.apply(x, a, keep, w0, b0, w1, b1)
 
     @staticmethod
     def mlp_residual2(x, xn, p0, p1, keep):
-        """mlp_residual of the stacked modalities; p0 / p1 = (w1, b1, w2, b2) of each (_HipMlpResidual2)."""
-        return _HipMlpResidual2.apply(x, xn, *p0, *p1, keep)
+        """mlp_residual of the stacked modalities; p0 / p1 = (w1, b1, w2, b2) of each (_HipMlp, two groups)."""
+        return _HipMlp.apply(x, xn, keep, *p0, *p1)
 
     @staticmethod
     def mam_attention(qkv, n_t, heads):

@@ -283,8 +283,8 @@ def test_module_forward_training_gpu_grads(variant, B):
     L2).  Round 6: the corner head's output convs x6 (the golden fixtures' gain) instead of x30, whose peaked
     score maps put torch-bf16 itself 22 % from fp32 (tools/grad_fixture_probe.py, profiles/r06_grad_fixture_probe.jsonl:
     x6 -> 8-9 %, x2 -> 6-8 %; the floor is the train-mode BatchNorm's batch statistics at B = 16), and a
-    negative control at B = 16: every two-stream Linear weight gradient scaled by 0.9 (mmt_amd.train._weight_grads2)
-    must fail the same check."""
+    negative control at B = 16: every two-stream Linear weight gradient scaled by 0.9 (the two-group calls of
+    mmt_amd.train._weight_grads) must fail the same check."""
     import sys
     import os
     sys.path.insert(0, os.path.dirname(__file__))
@@ -348,12 +348,16 @@ def test_module_forward_training_gpu_grads(variant, B):
     bad = check(hip, "hip")
     assert not bad, bad
     if variant == "rgbt" and B == 16:  # negative control: a 10 % weight-gradient error is flagged
-        orig = T._weight_grads2
-        T._weight_grads2 = lambda *a, **k: [(dw * 0.9, db * 0.9) for dw, db in orig(*a, **k)]
+        orig = T._weight_grads
+
+        def scaled(dy, *a, **k):  # the two-modality calls alone (a 2-tuple of operands); every other call as it is
+            out = orig(dy, *a, **k)
+            return [(dw * 0.9, db * 0.9) for dw, db in out] if isinstance(dy, tuple) and len(dy) == 2 else out
+        T._weight_grads = scaled
         try:
             _, neg = run(None, "cuda")
         finally:
-            T._weight_grads2 = orig
+            T._weight_grads = orig
         assert check(neg, "dW x0.9"), "the perturbed weight gradients passed the check"
 
 
@@ -614,13 +618,13 @@ def test_hip_layernorm_pass_through_gradient(two):
         assert torch.equal(a, b)
 
 
-def test_hip_mlp_autograd():
+@pytest.mark.parametrize("M,C,F4", [(1056, 768, 3072), (74, 64, 256)])
+def test_hip_mlp_autograd(M, C, F4):
     """HipOps.mlp (_HipMlp: fc1 with the GELU epilogue storing its pre-activation, fc2, and a backward
     whose fc2 dX GEMM applies GELU' in its epilogue) against the same MLP as torch fp32 autograd on the
     bf16-rounded operands (timm Mlp, mixformer.py:136-139): output and every gradient."""
     from mmt_amd.train import HipOps
     g = torch.Generator().manual_seed(17)
-    M, C, F4 = 1056, 768, 3072
     x = torch.randn(M, C, generator=g).bfloat16()
     w1 = torch.randn(F4, C, generator=g) / math.sqrt(C)
     b1 = torch.randn(F4, generator=g) * 0.1
@@ -645,15 +649,20 @@ def test_hip_mlp_autograd():
         assert err <= 2e-2, (name, err)
 
 
-@pytest.mark.parametrize("drop", [False, True])
-def test_hip_fused_residual_branches(drop):
-    """HipOps.linear_residual / mlp_residual (_HipLinearResidual / _HipMlpResidual: the block's proj and
+# (drop, B, ntok, C, F4) of the residual-branch Functions' tests: the ViT-B block at 4 samples, and M = B ntok = 74 rows
+# per group (74 % 8 = 2: the weight gradients take the padded transposing form, per group, while dX stays grouped)
+_BLOCK_SHAPES = [pytest.param(drop, *shape, id=str(drop) + tag)
+                 for shape, tag in (((4, 264, 768, 3072), ""), ((2, 37, 64, 256), "-M74")) for drop in (False, True)]
+
+
+@pytest.mark.parametrize("drop,B,ntok,C,F4", _BLOCK_SHAPES)
+def test_hip_fused_residual_branches(drop, B, ntok, C, F4):
+    """HipOps.linear_residual / mlp_residual (_HipLinearResidual / _HipMlp with its residual: the block's proj and
     MLP with DropPath and the residual add in the GEMM epilogue, row_scale = keep[m // ntok]) against
     x + keep * branch(a) in torch fp32 autograd on the bf16 operands: outputs and every gradient, with
     keep = (1 / (1 - p), 0, 1 / (1 - p), 1 / (1 - p)) (a dropped sample) or None."""
     from mmt_amd.train import HipOps
     g = torch.Generator().manual_seed(23)
-    B, ntok, C, F4 = 4, 264, 768, 3072
     M = B * ntok
     x = torch.randn(B, ntok, C, generator=g)
     a = torch.randn(M, C, generator=g).bfloat16()
@@ -664,7 +673,7 @@ def test_hip_fused_residual_branches(drop):
     w2 = torch.randn(C, F4, generator=g) / math.sqrt(F4)
     b2 = torch.randn(C, generator=g) * 0.1
     dy = torch.randn(B, ntok, C, generator=g)
-    keep = torch.tensor([1 / 0.9, 0.0, 1 / 0.9, 1 / 0.9]) if drop else None
+    keep = torch.tensor([1 / 0.9, 0.0, 1 / 0.9, 1 / 0.9][:B]) if drop else None
     F = torch.nn.functional
     cases = (("linear", HipOps.linear_residual, [w, b], lambda t, ps: F.linear(t, ps[0], ps[1])),
              ("mlp", HipOps.mlp_residual, [w1, b1, w2, b2],
@@ -1466,15 +1475,14 @@ def test_train_step_graph_replay_matches_eager():
         graphed.replay(*batches[0])
 
 
-@pytest.mark.parametrize("drop", [False, True])
-def test_hip_lockstep_pair_functions(drop):
+@pytest.mark.parametrize("drop,B,ntok,C,F4", _BLOCK_SHAPES)
+def test_hip_lockstep_pair_functions(drop, B, ntok, C, F4):
     """HipOps.linear2 / linear_residual2 / mlp_residual2 (the two-stream backbones in lockstep: rows [0, M)
     with the RGB weights, [M, 2M) with the TIR weights, grouped GEMMs forward and backward, per-modality
     launches for the DropPath row scale) against torch fp32 autograd on the bf16 operands, per half:
     outputs and every gradient within 2e-2 of the largest magnitude, as the one-modality Functions."""
     from mmt_amd.train import HipOps
     g = torch.Generator().manual_seed(31)
-    B, ntok, C, F4 = 4, 264, 768, 3072
     M = B * ntok
     F = torch.nn.functional
     x = torch.randn(2 * B, ntok, C, generator=g)
@@ -1483,7 +1491,10 @@ def test_hip_lockstep_pair_functions(drop):
     mlp = [[torch.randn(F4, C, generator=g) / math.sqrt(C), torch.randn(F4, generator=g) * 0.1,
             torch.randn(C, F4, generator=g) / math.sqrt(F4), torch.randn(C, generator=g) * 0.1] for _ in range(2)]
     dy = torch.randn(2 * B, ntok, C, generator=g)
-    keep = torch.tensor([1 / 0.9, 0.0, 1 / 0.9, 1 / 0.9, 0.0, 1 / 0.9, 1 / 0.9, 1 / 0.9]) if drop else None
+    keep = None
+    if drop:  # one dropped sample per modality
+        keep = torch.full((2 * B,), 1 / 0.9)
+        keep[1] = keep[B] = 0.0
 
     def run(kind, xd, ad, ps):
         if kind == "linear2":

@@ -51,15 +51,16 @@ def main():
         net.cuda()
         tb_loss, tb = run(_TorchBf16Ops, "cuda")
         hip_loss, hip = run(None, "cuda")
-        orig = T._weight_grads2
+        orig = T._weight_grads
 
-        def bad_wg2(*a, **k):
-            return [(dw * 0.9, db * 0.9) for dw, db in orig(*a, **k)]
-        T._weight_grads2 = bad_wg2
+        def bad_wg(dy, *a, **k):  # the two-modality calls alone (a 2-tuple of operands)
+            out = orig(dy, *a, **k)
+            return [(dw * 0.9, db * 0.9) for dw, db in out] if isinstance(dy, tuple) and len(dy) == 2 else out
+        T._weight_grads = bad_wg
         try:
             _, neg = run(None, "cuda")
         finally:
-            T._weight_grads2 = orig
+            T._weight_grads = orig
         row = {"gain": gain, "B": B, "loss": [ref_loss, tb_loss, hip_loss]}
         for grp in ("backbone_v", "backbone_i", "fusion_vi", "box_head"):
             names = [n for n in ref if n.startswith(grp + ".")]

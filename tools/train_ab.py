@@ -56,6 +56,8 @@ def accumulated_grads():
     saved = train._weight_grads, optim.HipAdamW.__init__, optim.HipAdamW.zero_grad
 
     def weight_grads(dy, x, M, N, K):
+        if isinstance(dy, tuple):  # the grouped form: per group
+            return [weight_grads(u, v, M, N, K) for u, v in zip(dy, x)]
         Mp = (M + 7) // 8 * 8
         dwb = train._gemm(train._transpose(dy, M, N, Mp), train._transpose(x, M, K, Mp, ones_row=True), N, K + 8,
                           Mp, out_f32=True)
@@ -72,17 +74,6 @@ def accumulated_grads():
         yield
     finally:
         train._weight_grads, optim.HipAdamW.__init__, optim.HipAdamW.zero_grad = saved
-
-
-@contextlib.contextmanager
-def transposed_copies():
-    """The Linear backward through transposed operand copies (mmt_transpose_bf16) instead of MN-major reads."""
-    from mmt_amd import train
-    train.MN_MAJOR = False
-    try:
-        yield
-    finally:
-        train.MN_MAJOR = True
 
 
 @contextlib.contextmanager
@@ -107,17 +98,6 @@ def aten_scale_cast():
 
 
 @contextlib.contextmanager
-def dual_stream():
-    """The pair backward's weight-gradient GEMMs on a side stream beside the input-gradient GEMMs."""
-    from mmt_amd import train
-    train.DUAL_STREAM = True
-    try:
-        yield
-    finally:
-        train.DUAL_STREAM = False
-
-
-@contextlib.contextmanager
 def sequential_backbones():
     """The two-stream backbones one after the other (one-group GEMMs) instead of backbone_forward_pair."""
     from mmt_amd import train
@@ -138,9 +118,8 @@ def main():
     args = ap.parse_args()
     variants = {"hip": HipOps, "aten_groupnorm": AtenGroupNormOps, "aten_layernorm": AtenLayerNormOps,
                 "split_mlp": SplitMlpOps, "unfused_residual": UnfusedResidualOps, "accum_grads": (HipOps, accumulated_grads),
-                "transposed": (HipOps, transposed_copies), "aten_scale_cast": (HipOps, aten_scale_cast),
-                "sequential": (HipOps, sequential_backbones), "composed_encoder": ComposedEncoderOps,
-                "dual_stream": (HipOps, dual_stream)}
+                "aten_scale_cast": (HipOps, aten_scale_cast), "sequential": (HipOps, sequential_backbones),
+                "composed_encoder": ComposedEncoderOps}
     if args.only:
         variants = {k: v for k, v in variants.items() if k in args.only.split(",")}
     for r in range(args.rounds):

@@ -48,12 +48,12 @@ def main():
             for cfg in args.cfgs.split(","):
                 impl, nsk = (int(v) for v in cfg.split(":"))
                 if kind == "dW":
-                    fn = lambda: T._gemm(T._halves(dy, M), T._halves(x, M), N, K + 8, M, out_f32=True, c=dws,  # noqa
+                    fn = lambda: T._gemm(T._groups(dy, 2), T._groups(x, 2), N, K + 8, M, out_f32=True, c=dws,  # noqa
                                          ldc=K, c2=dbs, c2_copy=3, a_t=1, w_t=2, ldw=K, lda=N, splitk=True,
                                          impl=impl, nsk=nsk)
                 else:
-                    act, r = (5, T._halves(hp, M)) if name == "fc2" else (0, None)  # fc2's dX: times GELU'(hp)
-                    fn = lambda: T._gemm(T._halves(dy, M), tuple(w), M, K, N, act=act, r=r, w_t=1, ldw=K,  # noqa
+                    act, r = (5, T._groups(hp, 2)) if name == "fc2" else (0, None)  # fc2's dX: times GELU'(hp)
+                    fn = lambda: T._gemm(T._groups(dy, 2), tuple(w), M, K, N, act=act, r=r, w_t=1, ldw=K,  # noqa
                                          impl=impl, splitk=nsk > 0, nsk=nsk)
                 try:
                     out = fn()
