@@ -124,10 +124,14 @@ typedef struct {
                      workgroups per CU (64 KiB ring; same restrictions as 7; auto on big unsplit grids),
                      9 (A/B builds only, MMT_GEMM_AB) 256x256 at one wave per SIMD (4 waves of 128x128
                      with AGPR accumulators; plain GEMM mode, ln_fold 0 / 2, row_scale),
-                     10 as 0, but a parameter set that impl 0 / 1 / 3 would hand to a lean frame kernel (the
-                     batch-1 ViT GEMMs: one round of workgroups, <= 2 groups, plain rows, K % 64 == 0; ln_fold 2
-                     with a 16-bit C at 128x128, or the fp32 residual producer with c2_copy 1 and ln_stats_out
-                     at 64x64) runs the general kernel at that tile shape, unsplit: bit-identical (A/B, tests) */
+                     10 as 0, but a parameter set that impl 0 / 1 / 2 / 3 would hand to a lean frame kernel (the
+                     batch-1 frame's GEMM-mode launches: one round of workgroups, <= 2 groups, plain rows, a bias,
+                     K % 64 == 0, R rows plain or r_mode 1 with r_p0 >= M; ln_fold 2 with a 16-bit C at 128x128;
+                     at 64x64 the fp32 residual producer with c2_copy 1 and ln_stats_out, an fp32 C = acc + bias
+                     (+ R) without C2, also with a1 / k_split % 64 == 0, and a 16-bit C = acc + bias; at 128x64 a
+                     16-bit C = relu(acc + bias)) runs the general kernel at that tile shape, unsplit:
+                     bit-identical (A/B, tests).  mmt_gemm_multi: as 0, but never the lean multi kernel (two
+                     problems, a 16-bit C = acc + bias beside an fp32 C = acc (+ bias) + R with a1, one round) */
     /* LayerNorm folded into the GEMM (bf16 LDS-DMA kernels, GEMM mode): A holds the raw rows x
      * (K = the LayerNorm width), W = W_lin * gamma (per column k), and the epilogue's v is
      *   rstd_m * (acc - mu_m * ln_colsum[g][n]) + bias[g][n],   mu / rstd over the K values of row m

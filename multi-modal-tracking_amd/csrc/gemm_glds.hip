@@ -23,6 +23,7 @@
 #include "gemm_internal.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 // MMT_GEMM_ABLATE (measurement builds only, tools/build_ablate.sh): 3 = no epilogue C / C2 stores,
 // 4 = no epilogue tile reads (constants instead); 1 = no DMA after the prologue
@@ -133,12 +134,19 @@ struct gemm_lean_null {  // a per-group pointer the path never has
 struct gemm_lean_fixed {  // plain GEMM mode, identity row maps, no split-K
     static constexpr int64_t a_seg_rows = INT32_MAX, a_segs_a = 1, a_stride_a = 0, a_stride_b = 0;
     static constexpr int64_t c_seg_rows = 0, c_seg_pitch = 0;
-    static constexpr int32_t k_split = 0, conv_h = 0, conv_up = 1, conv_cin = 0, conv_k3 = 0;
+    static constexpr int32_t conv_h = 0, conv_up = 1, conv_cin = 0, conv_k3 = 0;
     static constexpr int32_t r_mode = 0, r_p0 = 1, r_p1 = 1, r_t = 0;
     static constexpr float* sk_ws = nullptr;
     static constexpr uint32_t* sk_cnt = nullptr;
     static constexpr int64_t sk_cnt_n = 0;
+};
+struct gemm_lean_a_one {  // A from one pointer
+    static constexpr int32_t k_split = 0;
     gemm_lean_null a1;
+};
+struct gemm_lean_a_two {  // A from two pointers: columns [0, k_split) from a, the others from a1 (k_split % 64 == 0)
+    const void* a1[2];
+    int32_t k_split;
 };
 struct gemm_lean_grid {  // host-computed, the same for every workgroup
     int32_t per_g;       // tiles per group
@@ -146,11 +154,17 @@ struct gemm_lean_grid {  // host-computed, the same for every workgroup
     int32_t q8, r8;      // workgroups / 8 and % 8 (XCD remap)
     float inv_k;         // 1 / K
 };
-template <int EPI, int ACT>
+// FORM 0: the ViT forms below.  The frame's other GEMM-mode launches (patch embed aside, which is proj's form once
+// its identity row map is recognised) have the same epilogues without the hand-offs -- LEAN_PLAIN, with
+//   EPI 2: LEAN_R = R is added (else there is none), LEAN_A2 = A from two pointers, LEAN_OPTB = the bias may be
+//          absent (the offsets Linear of the multi launch, whose positional term arrives as R);
+//   EPI 1: no LayerNorm fold (LNM 0), ACT 0 / 2.
+constexpr int LEAN_PLAIN = 1, LEAN_R = 2, LEAN_A2 = 4, LEAN_OPTB = 8;
+template <int EPI, int ACT, int FORM = 0>
 struct gemm_lean_args;
 // EPI 1: 16-bit C = act(LayerNorm fold on handed-in statistics + bias)  (qkv, fc1)
 template <int ACT>
-struct gemm_lean_args<1, ACT> : gemm_lean_fixed, gemm_lean_grid {
+struct gemm_lean_args<1, ACT, 0> : gemm_lean_fixed, gemm_lean_a_one, gemm_lean_grid {
     const void *a[2], *w[2];
     const float *bias[2], *ln_colsum[2], *ln_stats_in[2];
     void* c[2];
@@ -159,9 +173,9 @@ struct gemm_lean_args<1, ACT> : gemm_lean_fixed, gemm_lean_grid {
     static constexpr int32_t act = ACT, c2_copy = 0, ldr = 0;
     gemm_lean_null r, c2, ln_stats_out;
 };
-// EPI 2: fp32 C = acc + bias + R, C2 its 16-bit copy, the next LayerNorm's row statistics  (proj, fc2)
-template <int ACT>
-struct gemm_lean_args<2, ACT> : gemm_lean_fixed, gemm_lean_grid {
+// EPI 2: fp32 C = acc + bias + R, C2 its 16-bit copy, the next LayerNorm's row statistics  (proj, fc2, patch embed)
+template <>
+struct gemm_lean_args<2, 0, 0> : gemm_lean_fixed, gemm_lean_a_one, gemm_lean_grid {
     const void *a[2], *w[2];
     const float *bias[2], *r[2];
     void *c[2], *c2[2];
@@ -171,10 +185,51 @@ struct gemm_lean_args<2, ACT> : gemm_lean_fixed, gemm_lean_grid {
     static constexpr float ln_eps = 0.f;
     gemm_lean_null ln_colsum, ln_stats_in;
 };
+// EPI 1, plain: 16-bit C = act(acc + bias)  (enc_linear1 with ReLU; the value Linear without)
+template <int ACT>
+struct gemm_lean_args<1, ACT, LEAN_PLAIN> : gemm_lean_fixed, gemm_lean_a_one, gemm_lean_grid {
+    const void *a[2], *w[2];
+    const float* bias[2];
+    void* c[2];
+    int32_t M, N, K, lda, ldc;
+    static constexpr int32_t act = ACT, c2_copy = 0, ldr = 0;
+    static constexpr float ln_eps = 0.f;
+    gemm_lean_null r, c2, ln_stats_out, ln_colsum, ln_stats_in;
+};
+// EPI 2, plain: fp32 C = acc + bias (+ R)  (fusion_adjust, enc_outproj; enc_linear2 with R; with two A pointers
+// fusion_adjust_cat and the offsets Linear)
+struct gemm_lean_f32_r {
+    const float* r[2];
+    int32_t ldr;
+};
+struct gemm_lean_f32_nor {
+    static constexpr int32_t ldr = 0;
+    gemm_lean_null r;
+};
+template <int FORM>
+struct gemm_lean_args<2, 0, FORM>
+    : gemm_lean_fixed, std::conditional_t<(FORM & LEAN_A2) != 0, gemm_lean_a_two, gemm_lean_a_one>,
+      std::conditional_t<(FORM & LEAN_R) != 0, gemm_lean_f32_r, gemm_lean_f32_nor>, gemm_lean_grid {
+    static_assert(FORM & LEAN_PLAIN, "the hand-off form is FORM 0");
+    const void *a[2], *w[2];
+    const float* bias[2];
+    void* c[2];
+    int32_t M, N, K, lda, ldc;
+    static constexpr int32_t act = 0, c2_copy = 0;
+    static constexpr float ln_eps = 0.f;
+    gemm_lean_null c2, ln_stats_out, ln_colsum, ln_stats_in;
+};
+// The tile's LDS.  One array per size, whichever instantiation of gemm_glds_tile asks: the two problems of a lean multi
+// launch (two argument types, hence two instantiations in one kernel) share it.
+template <int BYTES>
+MMT_DEV unsigned char* gemm_lds() {
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[BYTES];
+    return lds;
+}
 template <typename P>
-struct gemm_is_lean { static constexpr bool value = false; };
-template <int EPI, int ACT>
-struct gemm_is_lean<gemm_lean_args<EPI, ACT>> { static constexpr bool value = true; };
+struct gemm_is_lean { static constexpr bool value = false; static constexpr int form = 0; };
+template <int EPI, int ACT, int FORM>
+struct gemm_is_lean<gemm_lean_args<EPI, ACT, FORM>> { static constexpr bool value = true; static constexpr int form = FORM; };
 
 // WGM x WGN waves per k-group own WM x WN sub-tiles; KS k-groups split the K-steps.  CONV: A is
 // the implicit im2col of an NHWC 3x3/pad-1 (conv_k3) or 1x1 convolution, input read through the
@@ -212,11 +267,12 @@ MMT_DEV void gemm_glds_tile(const P& p, const int g, const int tile, const int s
     static_assert(KS == 1 || BM * BN * 4 <= KS * ST * STAGE, "k-group reduction buffer");
     // impl 9: its half-tile fp32 image (128 x 260 floats) and the row statistics exceed the 128 KiB ring
     constexpr bool LEAN = gemm_is_lean<P>::value;  // a lean frame kernel's argument block
-    static_assert(!LEAN || (OCC == 1 && !CONV && !RS && (LNM == 0 || LNM == 2) && BM * BN <= 128 * 128 &&
-                            ((EPI == 1 && LNM == 2) || (EPI == 2 && LNM == 0))), "lean frame kernels");
+    constexpr int LFORM = gemm_is_lean<P>::form;   // (its form: 0 = with the ViT hand-offs, else LEAN_PLAIN | ...)
+    static_assert(!LEAN || (OCC == 1 && !CONV && !RS && BM * BN <= 128 * 128 &&
+                            ((EPI == 1 && LNM == (LFORM ? 0 : 2)) || (EPI == 2 && LNM == 0))), "lean frame kernels");
     constexpr int LDS_BYTES = W4 ? (BM / 2) * (BN + 4) * 4 + BM * 8 + 64 : KS * ST * STAGE;
     static_assert(LDS_BYTES >= KS * ST * STAGE && LDS_BYTES <= 160 * 1024, "LDS budget");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
+    unsigned char* const lds = gemm_lds<LDS_BYTES>();
     MMT_STAMP(0, "s_memrealtime");
     MMT_STAMP(1, "s_memtime");
 
@@ -712,7 +768,8 @@ MMT_DEV void gemm_glds_tile(const P& p, const int g, const int tile, const int s
         }
     };
     f32x4 rpa[RPRE ? NPASS0 : 1], rpb[RPRE ? NPASS0 : 1];
-    if constexpr (LEAN && EPI == 2) __builtin_assume(p.r[g] != nullptr);  // (the launcher checks)
+    constexpr bool LEAN_HAS_R = LEAN && EPI == 2 && (LFORM == 0 || (LFORM & LEAN_R));
+    if constexpr (LEAN_HAS_R) __builtin_assume(p.r[g] != nullptr);  // (the launcher checks)
     const bool rpre = RPRE && p.r[g] != nullptr && nsk == 1;  // wave-uniform
     if constexpr (RPRE) {
         if (rpre) {
@@ -932,9 +989,9 @@ MMT_DEV void gemm_glds_tile(const P& p, const int g, const int tile, const int s
     }
 #endif
     if constexpr (LEAN) {  // present in every lean launch (the launcher checks)
-        __builtin_assume(bias != nullptr);
-        if constexpr (EPI == 2) {
-            __builtin_assume(R != nullptr);
+        if constexpr (!(LFORM & LEAN_OPTB)) __builtin_assume(bias != nullptr);
+        if constexpr (LEAN_HAS_R) __builtin_assume(R != nullptr);
+        if constexpr (EPI == 2 && LFORM == 0) {
             __builtin_assume(C2 != nullptr);
             __builtin_assume(p.ln_stats_out[g] != nullptr);
         }
@@ -1229,14 +1286,41 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS)
 // (<= 256 workgroups, <= 2 groups, no split-K) in the linear order of gemm_glds_kernel's (tiles, 1, groups) grid, so
 // the XCD placement, the tile a workgroup computes and every sum's order are those of gemm_glds_kernel at the same
 // tile shape: the outputs are bit-identical to it (tests/test_gpu_gemm_frame_kernels.py; impl 10 forces that kernel).
-template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT>
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT, int FORM = 0>
 __global__ __launch_bounds__(64 * WGM * WGN * KS)
     __attribute__((amdgpu_waves_per_eu(WGM * WGN * KS / 4, WGM * WGN * KS / 4))) void gemm_glds_frame_kernel(
-        const gemm_lean_args<EPI, ACT> p) {
+        const gemm_lean_args<EPI, ACT, FORM> p) {
     const int orig = blockIdx.x, xcd = orig & 7;
     const int lin = xcd * p.q8 + min(xcd, p.r8) + (orig >> 3);  // gemm_xcd_lin
     const int g = lin >= p.per_g ? 1 : 0;
     gemm_glds_tile<T, BM, BN, WGM, WGN, KS, ST, false, LNM, 1, false, EPI>(p, g, lin - g * p.per_g, 0, 1, p.per_g);
+}
+
+// Lean multi launch: two independent problems, each with a lean argument block and compact epilogue of its own, in
+// the linear order of gemm_glds_multi_kernel (problem 0's workgroups, then problem 1's; the XCD remap over the
+// union, q8 / r8 below), so every tile is computed as that kernel computes it: bit-identical outputs.
+template <typename P0, typename P1>
+struct gemm_lean_multi_args {
+    P0 p0;
+    P1 p1;
+    int32_t wg1;     // problem 1's first workgroup
+    int32_t q8, r8;  // of the union
+};
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int EPI0, typename P0, int EPI1, typename P1>
+__global__ __launch_bounds__(64 * WGM * WGN * KS)
+    __attribute__((amdgpu_waves_per_eu(WGM * WGN * KS / 4, WGM * WGN * KS / 4))) void gemm_glds_frame_multi_kernel(
+        const gemm_lean_multi_args<P0, P1> a) {
+    const int orig = blockIdx.x, xcd = orig & 7;
+    const int lin = xcd * a.q8 + min(xcd, a.r8) + (orig >> 3);  // gemm_xcd_lin
+    if (lin < a.wg1) {  // wave-uniform (scalar)
+        const int g = lin >= a.p0.per_g ? 1 : 0;
+        gemm_glds_tile<T, BM, BN, WGM, WGN, KS, ST, false, 0, 1, false, EPI0>(a.p0, g, lin - g * a.p0.per_g, 0, 1,
+                                                                             a.p0.per_g);
+    } else {
+        const int loc = lin - a.wg1, g = loc >= a.p1.per_g ? 1 : 0;
+        gemm_glds_tile<T, BM, BN, WGM, WGN, KS, ST, false, 0, 1, false, EPI1>(a.p1, g, loc - g * a.p1.per_g, 0, 1,
+                                                                             a.p1.per_g);
+    }
 }
 
 // The same tile at two workgroups per CU (impl 8: 128x128, 8 waves, 2-slot ring = 64 KiB of LDS, <= 128
@@ -1430,52 +1514,95 @@ int64_t tiles_of(const mmt_gemm_params& p, int bm, int bn) {
 // launches for qkv / fc1 (LayerNorm fold on handed-in statistics, compact 16-bit epilogue, 128x128) and proj / fc2
 // (compact residual producer with the 16-bit copy and the statistics hand-off, 64x64 with two k-groups) -- plain
 // rows, K % 64 == 0, <= 2 groups, one round of workgroups.  (glds_takes has checked alignment and the hand-off.)
-int lean_cfg(const mmt_gemm_params& p) {
-    if (p.groups > 2 || p.K % 64 || p.conv_h > 0 || p.k_split || p.a_seg_rows < p.M || p.c_seg_rows || p.a_t || p.w_t ||
+//
+// The frame's other GEMM-mode launches take the same epilogues without the hand-offs (LEAN_PLAIN forms), each at the
+// tile shape the cost model picks for it in the frame: fp32 C = acc + bias (+ R), A from one pointer or two, at 64x64
+// (fusion_adjust, enc_outproj, enc_linear2, fusion_adjust_cat); 16-bit C = acc + bias at 64x64 (the value Linear) and
+// with ReLU at 128x64 (enc_linear1).  *form receives the argument block's FORM.  opt_bias: a problem of a multi launch,
+// whose fp32 form takes an absent bias (the offsets Linear).
+// p is the launcher's view of the parameter set (lean_view below).
+int lean_cfg(const mmt_gemm_params& p, int* form = nullptr, bool opt_bias = false) {
+    if (p.groups > 2 || p.K % 64 || p.conv_h > 0 || p.a_seg_rows < p.M || p.c_seg_rows || p.a_t || p.w_t ||
         p.row_scale || p.splitk >= 2 || std::max({p.lda, p.ldc, p.ldr}) > INT32_MAX)  // (a forced K split is honoured)
         return 0;
-    for (int g = 0; g < p.groups; ++g)
-        if (!p.bias[g]) return 0;
-    int cfg = 0;
-    if (p.ln_fold == 2 && p.c2_copy == 0 && p.act <= 1 && compact_epilogue(p)) {
+    bool has_bias = p.bias[0] != nullptr, has_r = p.r[0] != nullptr;
+    for (int g = 0; g < p.groups; ++g)  // present in every group or in none
+        if ((p.bias[g] != nullptr) != has_bias || (p.r[g] != nullptr) != has_r) return 0;
+    int cfg = 0, f = 0;
+    if (p.k_split) {  // A from two pointers: the plain fp32 form alone, the boundary between two K-steps
+        if (p.k_split % 64 || p.k_split >= p.K || p.ln_fold || !residual_epilogue(p) || p.c2[0] || p.c2[p.groups - 1])
+            return 0;
+        cfg = 3, f = LEAN_PLAIN | LEAN_A2 | (has_r ? LEAN_R : 0);
+    } else if (p.ln_fold == 2 && p.c2_copy == 0 && p.act <= 1 && compact_epilogue(p)) {
         cfg = 1;
     } else if (p.ln_fold == 0 && residual_epilogue(p)) {
-        for (int g = 0; g < p.groups; ++g)
-            if (!p.r[g] || !p.c2[g] || !p.ln_stats_out[g]) return 0;
-        cfg = 3;
+        bool any = false, all = true;  // C2 with the statistics (the hand-off form), or neither
+        for (int g = 0; g < p.groups; ++g) {
+            const bool h = p.c2[g] && p.ln_stats_out[g];
+            if (!h && (p.c2[g] || p.ln_stats_out[g])) return 0;
+            any |= h, all &= h;
+        }
+        if (any != all || (all && !has_r)) return 0;
+        cfg = 3, f = all ? 0 : LEAN_PLAIN | (has_r ? LEAN_R : 0);
+    } else if (p.ln_fold == 0 && p.c2_copy == 0 && (p.act == 0 || p.act == 2) && compact_epilogue(p)) {
+        cfg = p.act == 2 ? 2 : 3, f = LEAN_PLAIN;
     } else {
         return 0;
     }
+    if (!has_bias) {
+        if (!(opt_bias && (f & LEAN_PLAIN) && p.c_f32)) return 0;
+        f |= LEAN_OPTB;
+    }
+    if (form) *form = f;
     return tiles_of(p, kCands[cfg - 1].bm, kCands[cfg - 1].bn) * p.groups <= 256 ? cfg : 0;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT>
-void launch_lean(const mmt_gemm_params& p, hipStream_t st) {
-    gemm_lean_args<EPI, ACT> a{};
-    const int tiles_m = (p.M + BM - 1) / BM, nwg = (int)tiles_of(p, BM, BN) * p.groups;
-    a.per_g = nwg / p.groups;
+// The launcher's view of a parameter set: r_mode 1 (R row = m % r_p0) with r_p0 >= M is the identity map (the patch
+// embed's positional rows and the offsets Linear's at one frame per group), i.e. r_mode 0.  The selection and the lean
+// argument blocks read this view; a general kernel gets the caller's struct.
+mmt_gemm_params lean_view(const mmt_gemm_params& p) {
+    mmt_gemm_params v = p;
+    if (v.r_mode == 1 && v.r_p0 >= v.M) v.r_mode = 0;
+    return v;
+}
+
+// Fills the lean argument block of one problem; nwg_all: the workgroups of the launch (the XCD remap's split).
+template <int BM, int BN, int EPI, int ACT, int FORM>
+void fill_lean(gemm_lean_args<EPI, ACT, FORM>& a, const mmt_gemm_params& p, int nwg_all) {
+    const int tiles_m = (p.M + BM - 1) / BM;
+    a.per_g = (int)tiles_of(p, BM, BN);
     a.tn_magic = 65536 / tiles_m + 1;  // exact while tile * tiles_m < 65536 (tile < 256, tiles_m <= 256)
-    a.q8 = nwg >> 3;
-    a.r8 = nwg & 7;
+    a.q8 = nwg_all >> 3;
+    a.r8 = nwg_all & 7;
     a.inv_k = 1.f / (float)p.K;
     for (int g = 0; g < p.groups; ++g) {
         a.a[g] = p.a[g];
         a.w[g] = p.w[g];
         a.bias[g] = p.bias[g];
         a.c[g] = p.c[g];
-        if constexpr (EPI == 1) {
+        if constexpr (EPI == 1 && FORM == 0) {
             a.ln_colsum[g] = p.ln_colsum[g];
             a.ln_stats_in[g] = p.ln_stats_in[g];
-        } else {
-            a.r[g] = p.r[g];
+        }
+        if constexpr (EPI == 2 && FORM == 0) {
             a.c2[g] = p.c2[g];
             a.ln_stats_out[g] = p.ln_stats_out[g];
         }
+        if constexpr (EPI == 2 && (FORM == 0 || (FORM & LEAN_R))) a.r[g] = p.r[g];
+        if constexpr ((FORM & LEAN_A2) != 0) a.a1[g] = p.a1[g];
     }
     a.M = p.M, a.N = p.N, a.K = p.K, a.lda = (int32_t)p.lda, a.ldc = (int32_t)p.ldc;
-    if constexpr (EPI == 1) a.ln_eps = p.ln_eps;
-    else a.ldr = (int32_t)p.ldr;
-    hipLaunchKernelGGL((gemm_glds_frame_kernel<T, BM, BN, WGM, WGN, KS, ST, LNM, EPI, ACT>), dim3(nwg),
+    if constexpr (EPI == 1 && FORM == 0) a.ln_eps = p.ln_eps;
+    if constexpr (EPI == 2 && (FORM == 0 || (FORM & LEAN_R))) a.ldr = (int32_t)p.ldr;
+    if constexpr ((FORM & LEAN_A2) != 0) a.k_split = p.k_split;
+}
+
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT, int FORM = 0>
+void launch_lean(const mmt_gemm_params& p, hipStream_t st) {
+    gemm_lean_args<EPI, ACT, FORM> a{};
+    const int nwg = (int)tiles_of(p, BM, BN) * p.groups;
+    fill_lean<BM, BN>(a, p, nwg);
+    hipLaunchKernelGGL((gemm_glds_frame_kernel<T, BM, BN, WGM, WGN, KS, ST, LNM, EPI, ACT, FORM>), dim3(nwg),
                        dim3(64 * WGM * WGN * KS), 0, st, a);
 }
 
@@ -1487,7 +1614,9 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
     if (force < 0 || !glds_takes(p)) return 1;
     // impl 10: gemm_glds_kernel where a lean frame kernel would run, at that kernel's tile shape and unsplit (A/B and
     // the bitwise test of the lean kernels); every other parameter set as impl 0
-    const int lcfg = lean_cfg(p);
+    const mmt_gemm_params pv = lean_view(p);
+    int lform = 0;
+    const int lcfg = lean_cfg(pv, &lform);
     const bool no_lean = force == 10;
     if (force == 10) force = lcfg;
     const int nk = (p.K + 63) / 64;
@@ -1614,10 +1743,17 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
             }
         }
     }
-    if (!no_lean && nsk == 1 && cfg != 0 && cfg == lcfg) {  // the tile shapes of cases 1 / 3 below
-        if (cfg == 3) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0>(p, st);
-        else if (p.act == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 1>(p, st);
-        else launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 0>(p, st);
+    if (!no_lean && nsk == 1 && cfg != 0 && cfg == lcfg) {  // the tile shapes of cases 1 / 2 / 3 below
+        constexpr int PL = LEAN_PLAIN, PR = LEAN_PLAIN | LEAN_R, A2 = LEAN_A2;
+        if (cfg == 1 && p.act == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 1>(pv, st);
+        else if (cfg == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 0>(pv, st);
+        else if (cfg == 2) launch_lean<T, 128, 64, 2, 2, 2, 3, 0, 1, 2, PL>(pv, st);
+        else if (lform == 0) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0>(pv, st);
+        else if (!p.c_f32) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 1, 0, PL>(pv, st);
+        else if (lform == PL) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL>(pv, st);
+        else if (lform == PR) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR>(pv, st);
+        else if (lform == (PL | A2)) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL | A2>(pv, st);
+        else launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR | A2>(pv, st);
         return 0;
     }
     switch (cfg) {
@@ -1671,20 +1807,47 @@ void launch_multi(const mmt_gemm_params* ps, int n, bool conv, hipStream_t st) {
     if (conv) hipLaunchKernelGGL((gemm_glds_multi_kernel<T, BM, BN, WGM, WGN, KS, ST, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((gemm_glds_multi_kernel<T, BM, BN, WGM, WGN, KS, ST, false>), grid, block, 0, st, a);
 }
+
+// The lean multi launch (gemm_glds_frame_multi_kernel) of the pair the frame's fusion encoder issues, at the 64x64
+// tile the cost model picks for it: a 16-bit C = acc + bias (the value Linear) beside an fp32 C = acc (+ bias) + R
+// with A from two pointers (the offsets Linear) -- every problem a lean form, the union one round.  false: not that.
+template <typename T>
+bool launch_lean_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
+    constexpr int BM = 64, BN = 64, F1 = LEAN_PLAIN | LEAN_R | LEAN_A2 | LEAN_OPTB;
+    using P0 = gemm_lean_args<1, 0, LEAN_PLAIN>;
+    using P1 = gemm_lean_args<2, 0, F1>;
+    if (n != 2) return false;
+    const mmt_gemm_params v0 = lean_view(ps[0]), v1 = lean_view(ps[1]);
+    int f0 = 0, f1 = 0;
+    if (lean_cfg(v0, &f0, true) != 3 || lean_cfg(v1, &f1, true) != 3) return false;
+    if (v0.c_f32 || f0 != LEAN_PLAIN || (f1 | LEAN_OPTB) != F1) return false;
+    const int wg0 = (int)tiles_of(v0, BM, BN) * v0.groups, wg1 = (int)tiles_of(v1, BM, BN) * v1.groups;
+    if (wg0 + wg1 > 256) return false;
+    gemm_lean_multi_args<P0, P1> a{};
+    fill_lean<BM, BN>(a.p0, v0, wg0 + wg1);
+    fill_lean<BM, BN>(a.p1, v1, wg0 + wg1);
+    a.wg1 = wg0;
+    a.q8 = (wg0 + wg1) >> 3;
+    a.r8 = (wg0 + wg1) & 7;
+    hipLaunchKernelGGL((gemm_glds_frame_multi_kernel<T, BM, BN, 2, 2, 2, 4, 1, P0, 2, P1>), dim3(wg0 + wg1), dim3(512),
+                       0, st, a);
+    return true;
+}
 }  // namespace
 
 // n independent GEMMs in one launch; returns 1 when some problem is not one the LDS-DMA kernel
 // takes in this mode (all GEMM or all conv, no folded LayerNorm, no split-K, one forced impl).  The
 // configuration is chosen once for the union: rounds of 256 workgroups over all problems times the
-// slowest problem's per-workgroup time (the cost model above).
+// slowest problem's per-workgroup time (the cost model above).  impl 10: as 0, but never the lean multi kernel.
 template <typename T>
 int mmt_gemm_glds_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
     if (n < 1 || n > GEMM_MULTI) return 1;
     const bool conv = ps[0].conv_h > 0;
-    const int force = ps[0].impl;
+    const bool no_lean = ps[0].impl == 10;
+    const int force = no_lean ? 0 : ps[0].impl;
     for (int i = 0; i < n; ++i) {
         const mmt_gemm_params& p = ps[i];
-        if (!glds_takes(p) || (p.conv_h > 0) != conv || p.ln_fold || p.impl != force || force < 0 || force > 4 ||
+        if (!glds_takes(p) || (p.conv_h > 0) != conv || p.ln_fold || p.impl != ps[0].impl || force < 0 || force > 4 ||
             p.a_t || p.w_t)
             return 1;
     }
@@ -1707,6 +1870,7 @@ int mmt_gemm_glds_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
     int64_t wg_total = 0;
     for (int i = 0; i < n; ++i) wg_total += tiles_of(ps[i], kCands[cfg - 1].bm, kCands[cfg - 1].bn) * ps[i].groups;
     if (wg_total > INT32_MAX) return 1;
+    if (cfg == 3 && !conv && !no_lean && launch_lean_multi<T>(ps, n, st)) return 0;
     switch (cfg) {
         case 1: launch_multi<T, 128, 128, 2, 4, 1, 4>(ps, n, conv, st); break;
         case 2: launch_multi<T, 128, 64, 2, 2, 2, 3>(ps, n, conv, st); break;
