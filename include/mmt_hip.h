@@ -201,6 +201,33 @@ int mmt_gemm(const mmt_gemm_params* p, int dtype, void* stream);
  * workgroups each. */
 int mmt_gemm_multi(const mmt_gemm_params* ps, int n, int dtype, void* stream);
 
+/* The kernel mmt_gemm / mmt_gemm_multi run for a parameter set: the host-side selection's whole answer, from which
+ * the launch is issued.  Fields that do not apply to the family are 0. */
+enum { MMT_GEMM_REJECTED = 0, MMT_GEMM_GEMV = 1, MMT_GEMM_REG_TILE = 2, MMT_GEMM_LDS_DMA = 3, MMT_GEMM_SEPARATELY = 4 };
+typedef struct mmt_gemm_choice {
+    int32_t family;  /* MMT_GEMM_*: rejected (MMT_EBADARG), the fp32 GEMV, the register-staged tiles, the LDS-DMA
+                        tiles; SEPARATELY (mmt_gemm_multi only): no joint launch, one mmt_gemm per problem */
+    int32_t bm, bn;  /* tile rows / columns (register tiles: 64x64 or 128x128; LDS-DMA: those of `cfg`) */
+    int32_t kgroups; /* wave groups that split the K-steps inside a workgroup (1 or 2) */
+    int32_t cfg;     /* LDS-DMA: the tile configuration 1..9 of the `impl` table above (what impl 0 / 10 resolved to) */
+    int32_t nsk;     /* LDS-DMA: K slices over workgroups (1: no split-K) */
+    int32_t epi;     /* LDS-DMA: epilogue code, 0 general, 1 compact 16-bit C, 2 compact fp32 residual producer */
+    int32_t lnm;     /* LDS-DMA: operand mode, 0 plain, 1 / 2 = ln_fold, 3 W MN-major, 4 A and W MN-major */
+    int32_t rs;      /* LDS-DMA: 1 the row-scale kernels */
+    int32_t conv;    /* 1 conv mode (implicit im2col) */
+    int32_t lean;    /* LDS-DMA: 1 a lean frame kernel (joint > 1: the lean multi kernel) */
+    int32_t form;    /* lean: 0 the ViT forms with the LayerNorm hand-offs, else bits 1 plain | 2 R added | 4 A from
+                        two pointers | 8 bias may be absent (joint launch: the form of problem 1) */
+    int32_t joint;   /* 0: mmt_gemm's launch of one problem; n >= 1: mmt_gemm_multi's joint launch of n problems */
+    int32_t wgs;     /* workgroups of the launch */
+} mmt_gemm_choice;
+
+/* Asks the selection without launching: n == 1 answers for mmt_gemm(ps, dtype), 2 <= n <= 4 for
+ * mmt_gemm_multi(ps, n, dtype), out[0] describing the joint launch or saying SEPARATELY.  Returns 0 or MMT_EBADARG
+ * exactly when the launching entry point would.  Host arithmetic only: no GPU is needed, and the pointers in ps are
+ * tested for NULL and alignment, never dereferenced. */
+int mmt_gemm_select(const mmt_gemm_params* ps, int n, int dtype, mmt_gemm_choice* out);
+
 /* ---------------------------------------------------------------- MAM attention
  * qkv: [S][ntok][3*C] (dtype) as produced by the fused qkv Linear (reshape(B,N,3,H,d) order);
  * out: [S][ntok][C].  Queries [0,n_t) attend keys [0,n_t) of their own sequence; queries

@@ -18,6 +18,8 @@
 #include "common.hpp"
 #include "gemm_internal.hpp"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int NCH = 8, DEPTH = 3;
@@ -265,29 +267,10 @@ __global__ __launch_bounds__(256 * KS) void gemm_kernel(const mmt_gemm_params p)
         }
 }
 
-template <typename T, bool CONV>
-void launch_tiles(const mmt_gemm_params& p, hipStream_t st) {
-    auto blocks = [&](int bm, int bn) { return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.groups; };
-    const int nk64 = (p.K + 16 / (int)sizeof(T) * NCH - 1) / (16 / (int)sizeof(T) * NCH);
-    // Large problems: 128x128 (best MFMA:LDS ratio).  Otherwise 64x64 to put work on every CU,
-    // with two k-groups per tile when there are enough K-steps to share.
-    if (blocks(128, 128) >= 512) {
-        dim3 grid((unsigned)(blocks(128, 128) / p.groups), 1, p.groups);
-        hipLaunchKernelGGL((gemm_kernel<T, CONV, 128, 128, 1>), grid, dim3(256), 0, st, p);
-    } else if (nk64 >= 8) {
-        dim3 grid((unsigned)(blocks(64, 64) / p.groups), 1, p.groups);
-        hipLaunchKernelGGL((gemm_kernel<T, CONV, 64, 64, 2>), grid, dim3(512), 0, st, p);
-    } else {
-        dim3 grid((unsigned)(blocks(64, 64) / p.groups), 1, p.groups);
-        hipLaunchKernelGGL((gemm_kernel<T, CONV, 64, 64, 1>), grid, dim3(256), 0, st, p);
-    }
-}
-
 // GEMV path for a handful of rows (the score head's single-token Linears, M = batch; its 16 ROI tokens): one wave per
 // output column n, lanes stride K with 16-B loads of the W row and the M activation rows, wave-sum,
 // + bias, activation.  The tiled kernels would stream W through one K loop per 64-column tile (a few
 // workgroups for the whole launch).  Plain fp32 GEMMs only: no residual / row maps / conv / split.
-constexpr int GEMV_MAXM = 16;
 __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__ a, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ c, int M,
                                                        int N, int K, int64_t lda, int64_t ldc, int act) {
@@ -361,22 +344,73 @@ int check_gemm(const mmt_gemm_params& p) {
     return 0;
 }
 
+// The selection, whole: argument checks, the GEMV test, the LDS-DMA family (gemm_glds_select), else the register tiles.
+// family MMT_GEMM_REJECTED is MMT_EBADARG.
 template <typename T>
-int launch_gemm(const mmt_gemm_params& p, hipStream_t st) {
-    if (const int e = check_gemm<T>(p)) return e;
+gemm_choice gemm_select(const mmt_gemm_params& p) {
+    gemm_choice c{};
+    if (check_gemm<T>(p)) return c;
+    c.conv = p.conv_h > 0;
     if (sizeof(T) == 4 && p.M <= GEMV_MAXM && p.groups == 1 && p.conv_h == 0 && !p.r[0] && !p.c2[0] && p.c_f32 &&
         p.k_split == 0 && !p.ln_fold && p.splitk == 0 && p.c_seg_rows == 0 && p.a_seg_rows >= p.M && p.K % 4 == 0 &&
         p.lda % 4 == 0 && p.impl <= 0) {
-        hipLaunchKernelGGL(gemv_f32_kernel, dim3((unsigned)((p.N + 3) / 4)), dim3(256), 0, st, (const float*)p.a[0],
+        c.family = MMT_GEMM_GEMV;
+        c.wgs = (p.N + 3) / 4;
+        return c;
+    }
+    if (sizeof(T) == 2 && gemm_glds_select(p, c)) return c;
+    if (p.ln_fold || p.c2_copy || p.act == 5 || p.w_t || p.row_scale) return gemm_choice{};  // LDS-DMA kernel features only
+    auto blocks = [&](int bm, int bn) { return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.groups; };
+    const int nk64 = (p.K + 16 / (int)sizeof(T) * NCH - 1) / (16 / (int)sizeof(T) * NCH);
+    // Large problems: 128x128 (best MFMA:LDS ratio).  Otherwise 64x64 to put work on every CU,
+    // with two k-groups per tile when there are enough K-steps to share.
+    c.family = MMT_GEMM_REG_TILE;
+    c.bm = c.bn = blocks(128, 128) >= 512 ? 128 : 64;
+    c.kgroups = c.bm == 64 && nk64 >= 8 ? 2 : 1;
+    c.wgs = (int32_t)blocks(c.bm, c.bn);
+    return c;
+}
+
+// mmt_gemm_multi's decision: one joint LDS-DMA launch, or SEPARATELY (each problem then selects for itself).
+template <typename T>
+gemm_choice gemm_select_multi(const mmt_gemm_params* ps, int n) {
+    gemm_choice c{};
+    if (n < 1 || n > 4) return c;
+    for (int i = 0; i < n; ++i)
+        if (check_gemm<T>(ps[i])) return c;
+    if (sizeof(T) != 2 || !gemm_glds_select_multi(ps, n, c)) c = gemm_choice{MMT_GEMM_SEPARATELY};
+    return c;
+}
+
+// Launches a choice of gemm_select / a joint choice of gemm_select_multi: with gemm_glds_launch the only code that
+// names kernel instantiations.
+template <typename T>
+void gemm_launch(const mmt_gemm_params* ps, const gemm_choice& c, hipStream_t st) {
+    const mmt_gemm_params& p = ps[0];
+    if (c.family == MMT_GEMM_GEMV) {
+        hipLaunchKernelGGL(gemv_f32_kernel, dim3((unsigned)c.wgs), dim3(256), 0, st, (const float*)p.a[0],
                            (const float*)p.w[0], (const float*)p.bias[0], (float*)p.c[0], p.M, p.N, p.K, p.lda, p.ldc,
                            p.act);
-        return launch_status();
+    } else if (c.family == MMT_GEMM_LDS_DMA) {
+        if constexpr (sizeof(T) == 2) gemm_glds_launch<T>(ps, c, st);
+    } else {
+        const dim3 grid((unsigned)(c.wgs / p.groups), 1, p.groups);
+        auto go = [&](auto conv) {
+            constexpr bool CONV = decltype(conv)::value;
+            if (c.bm == 128) hipLaunchKernelGGL((gemm_kernel<T, CONV, 128, 128, 1>), grid, dim3(256), 0, st, p);
+            else if (c.kgroups == 2) hipLaunchKernelGGL((gemm_kernel<T, CONV, 64, 64, 2>), grid, dim3(512), 0, st, p);
+            else hipLaunchKernelGGL((gemm_kernel<T, CONV, 64, 64, 1>), grid, dim3(256), 0, st, p);
+        };
+        if (c.conv) go(std::true_type{});
+        else go(std::false_type{});
     }
-    if constexpr (sizeof(T) == 2)
-        if (mmt_gemm_glds<T>(p, st, p.impl) == 0) return launch_status();
-    if (p.ln_fold || p.c2_copy || p.act == 5 || p.w_t || p.row_scale) return MMT_EBADARG;  // LDS-DMA kernel features only
-    if (p.conv_h > 0) launch_tiles<T, true>(p, st);
-    else launch_tiles<T, false>(p, st);
+}
+
+template <typename T>
+int launch_gemm(const mmt_gemm_params& p, hipStream_t st) {
+    const gemm_choice c = gemm_select<T>(p);
+    if (c.family == MMT_GEMM_REJECTED) return MMT_EBADARG;
+    gemm_launch<T>(&p, c, st);
     return launch_status();
 }
 
@@ -384,14 +418,24 @@ int launch_gemm(const mmt_gemm_params& p, hipStream_t st) {
 // else one launch each (same results up to the fp32 summation order of the chosen tile shapes).
 template <typename T>
 int launch_gemm_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
-    if (n < 1 || n > 4) return MMT_EBADARG;
-    for (int i = 0; i < n; ++i)
-        if (const int e = check_gemm<T>(ps[i])) return e;
-    if constexpr (sizeof(T) == 2)
-        if (mmt_gemm_glds_multi<T>(ps, n, st) == 0) return launch_status();
+    const gemm_choice c = gemm_select_multi<T>(ps, n);
+    if (c.family == MMT_GEMM_REJECTED) return MMT_EBADARG;
+    if (c.family == MMT_GEMM_LDS_DMA) {
+        gemm_launch<T>(ps, c, st);
+        return launch_status();
+    }
     for (int i = 0; i < n; ++i)
         if (const int e = launch_gemm<T>(ps[i], st)) return e;
     return 0;
+}
+
+template <typename T>
+int select_gemm(const mmt_gemm_params* ps, int n, gemm_choice* out) {
+    *out = n == 1 ? gemm_select<T>(ps[0]) : gemm_select_multi<T>(ps, n);
+    if (out->family == MMT_GEMM_SEPARATELY)  // as mmt_gemm_multi then answers: the first problem's error, if any
+        for (int i = 0; i < n; ++i)
+            if (gemm_select<T>(ps[i]).family == MMT_GEMM_REJECTED) *out = gemm_choice{};
+    return out->family == MMT_GEMM_REJECTED ? MMT_EBADARG : 0;
 }
 
 }  // namespace
@@ -409,5 +453,13 @@ extern "C" int mmt_gemm(const mmt_gemm_params* p, int dtype, void* stream) {
     if (dtype == MMT_BF16) return launch_gemm<bf16_t>(*p, (hipStream_t)stream);
     if (dtype == MMT_F16) return launch_gemm<f16_t>(*p, (hipStream_t)stream);
     if (dtype == MMT_F32) return launch_gemm<float>(*p, (hipStream_t)stream);
+    return MMT_EBADARG;
+}
+
+extern "C" int mmt_gemm_select(const mmt_gemm_params* ps, int n, int dtype, mmt_gemm_choice* out) {
+    if (!ps || !out) return MMT_EBADARG;
+    if (dtype == MMT_BF16) return select_gemm<bf16_t>(ps, n, out);
+    if (dtype == MMT_F16) return select_gemm<f16_t>(ps, n, out);
+    if (dtype == MMT_F32) return select_gemm<float>(ps, n, out);
     return MMT_EBADARG;
 }

@@ -1411,59 +1411,6 @@ bool residual_epilogue(const mmt_gemm_params& p, bool rs = false) {  // rs: a ro
     return true;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST>
-void launch(const mmt_gemm_params& p, int nsk, hipStream_t st) {
-    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    const dim3 grid(tiles, nsk, p.groups), block(64 * WGM * WGN * KS);
-    if (p.conv_h == 0 && p.ln_fold != 1 && compact_epilogue(p)) {  // (LayerNorm folded with handed-in statistics or none)
-        if (p.ln_fold == 2)
-            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 2, 1>), grid, block, 0, st, p);
-        else
-            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 0, 1>), grid, block, 0, st, p);
-        return;
-    }
-    if (p.conv_h == 0 && residual_epilogue(p)) {
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 0, 2>), grid, block, 0, st, p);
-        return;
-    }
-    if (p.conv_h > 0 && compact_epilogue(p))  // the corner head's plain conv + ReLU layers
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, true, 0, 1>), grid, block, 0, st, p);
-    else if (p.conv_h > 0)
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, true, 0>), grid, block, 0, st, p);
-    else if (p.ln_fold == 2)
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 2>), grid, block, 0, st, p);
-    else if (p.ln_fold)
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 1>), grid, block, 0, st, p);
-    else
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 0>), grid, block, 0, st, p);
-}
-
-// impl 9's launch: 1 when the mode is not one it takes (LayerNorm summed in the K loop, conv, MN-major operands)
-template <typename T>
-int launch_w4(const mmt_gemm_params& p, hipStream_t st) {
-#if !MMT_GEMM_AB
-    return 1;  // A/B build only
-#else
-    if ((p.ln_fold != 0 && p.ln_fold != 2) || p.conv_h > 0 || p.a_t || p.w_t) return 1;
-    const dim3 grid((unsigned)(((p.M + 255) / 256) * ((p.N + 255) / 256)), 1, p.groups), block(256);
-    if (p.row_scale) {
-        if (p.ln_fold) return 1;
-        if (residual_epilogue(p, true)) hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0, true, 2>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0, true>), grid, block, 0, st, p);
-    } else if (p.ln_fold == 2) {
-        if (compact_epilogue(p)) hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 2, false, 1>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 2>), grid, block, 0, st, p);
-    } else if (compact_epilogue(p)) {
-        hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0, false, 1>), grid, block, 0, st, p);
-    } else if (residual_epilogue(p)) {
-        hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0, false, 2>), grid, block, 0, st, p);
-    } else {
-        hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0>), grid, block, 0, st, p);
-    }
-    return 0;
-#endif
-}
-
 bool aligned(const void* ptr, int bytes) { return ((uintptr_t)ptr & (uintptr_t)(bytes - 1)) == 0; }
 
 // Whether the shape / layout is one the LDS-DMA kernel takes.
@@ -1502,13 +1449,51 @@ bool glds_takes(const mmt_gemm_params& p) {
 // Large-M tiles (impl 5 / 6: 256x128 / 128x256, 8 waves with 64x64 wave tiles, 3-slot ring of
 // 48 KiB stages): 1.5x the MFMA work per byte of LDS fill of 128x128, for grids of many rounds.
 struct Cand { int cfg, bm, bn, ks; float fixed_us, step_us; };
-constexpr Cand kCands[7] = {{1, 128, 128, 1, 6.0f, 0.52f}, {2, 128, 64, 2, 5.0f, 0.52f}, {3, 64, 64, 2, 3.2f, 0.33f},
+constexpr Cand kCands[9] = {{1, 128, 128, 1, 6.0f, 0.52f}, {2, 128, 64, 2, 5.0f, 0.52f}, {3, 64, 64, 2, 3.2f, 0.33f},
                             {4, 128, 128, 1, 6.0f, 0.60f}, {5, 256, 128, 1, 7.0f, 0.70f}, {6, 128, 256, 1, 7.0f, 0.70f},
-                            {7, 256, 256, 1, 9.0f, 1.33f}};
+                            {7, 256, 256, 1, 9.0f, 1.33f},
+                            {8, 128, 128, 1, 0.f, 0.f}, {9, 256, 256, 1, 0.f, 0.f}};  // (shapes only: never priced)
 int64_t tiles_of(const mmt_gemm_params& p, int bm, int bn) {
     return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
 }
+int64_t tiles_of(const mmt_gemm_params& p, const Cand& c) { return tiles_of(p, c.bm, c.bn); }
 
+// Largest K split the workspace allows for a candidate (each slice keeps >= ks K-steps).
+int max_split(const mmt_gemm_params& p, const Cand& c) {
+    if (p.ln_fold || !p.sk_ws || !p.sk_cnt) return 1;
+    const int64_t t = tiles_of(p, c) * p.groups;
+    if (2 * t > p.sk_cnt_n) return 1;  // a ticket and a published count per tile
+    const int nk = (p.K + 63) / 64;
+    int n = 8;
+    while (n > 1 && ((int64_t)n * c.ks > nk || t * n * c.bm * c.bn > p.sk_ws_floats)) --n;
+    return n;
+}
+
+// The model's time of np problems side by side in one launch of candidate c, each cut into n K slices: rounds of 256
+// workgroups over all of them times the slowest problem's workgroup, plus the split's partial round trip.
+float cost(const mmt_gemm_params* ps, int np, const Cand& c, int n) {
+    int64_t wg = 0;
+    float slowest = 0.f;
+    for (int i = 0; i < np; ++i) {
+        wg += tiles_of(ps[i], c) * ps[i].groups * n;
+        const int steps = ((ps[i].K + 63) / 64 + n - 1) / n;
+        slowest = std::max(slowest, c.fixed_us + (float)((steps + c.ks - 1) / c.ks) * c.step_us);
+    }
+    const float red = n > 1 ? 0.8f + 0.5f * (float)(n - 1) * (float)(c.bm * c.bn) / 16384.f : 0.f;
+    return (float)((wg + 255) / 256) * slowest + red;
+}
+
+// The search step every selection shares: candidate c at each K split the request allows (ps[0].splitk: 0 the model's
+// choice, 1 none, n >= 2 forced, clipped to max_split; split false: unsplit only), kept when it beats `best`.
+void try_cand(const mmt_gemm_params* ps, int np, const Cand& c, bool split, float& best, int& cfg, int& nsk) {
+    const int want = ps[0].splitk, ms = split ? max_split(ps[0], c) : 1;
+    const int nmax = want >= 1 ? std::min(want, ms) : ms;
+    for (int n = (want >= 2 ? nmax : 1); n <= nmax; ++n) {
+        // a split must win clearly: the model prices the partial round trip loosely
+        const float t = cost(ps, np, c, n) * (n > 1 && want == 0 ? 1.15f : 1.f);
+        if (t < best) best = t, cfg = c.cfg, nsk = n;
+    }
+}
 
 // The tile shape (impl 1 / 3) of the lean frame kernel that covers p, 0 if none does: what the batch-1 frame plan
 // launches for qkv / fc1 (LayerNorm fold on handed-in statistics, compact 16-bit epilogue, 128x128) and proj / fc2
@@ -1597,94 +1582,73 @@ void fill_lean(gemm_lean_args<EPI, ACT, FORM>& a, const mmt_gemm_params& p, int 
     if constexpr ((FORM & LEAN_A2) != 0) a.k_split = p.k_split;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT, int FORM = 0>
-void launch_lean(const mmt_gemm_params& p, hipStream_t st) {
-    gemm_lean_args<EPI, ACT, FORM> a{};
-    const int nwg = (int)tiles_of(p, BM, BN) * p.groups;
-    fill_lean<BM, BN>(a, p, nwg);
-    hipLaunchKernelGGL((gemm_glds_frame_kernel<T, BM, BN, WGM, WGN, KS, ST, LNM, EPI, ACT, FORM>), dim3(nwg),
-                       dim3(64 * WGM * WGN * KS), 0, st, a);
+// The lean multi launch (gemm_glds_frame_multi_kernel) covers the pair the frame's fusion encoder issues, at the 64x64
+// tile the cost model picks for it: a 16-bit C = acc + bias (the value Linear) beside an fp32 C = acc (+ bias) + R
+// with A from two pointers (the offsets Linear) -- every problem a lean form, the union one round.
+constexpr int LEAN_MULTI_F1 = LEAN_PLAIN | LEAN_R | LEAN_A2 | LEAN_OPTB;
+bool lean_multi(const mmt_gemm_params* ps, int n) {
+    if (n != 2) return false;
+    const mmt_gemm_params v0 = lean_view(ps[0]), v1 = lean_view(ps[1]);
+    int f0 = 0, f1 = 0;
+    if (lean_cfg(v0, &f0, true) != 3 || lean_cfg(v1, &f1, true) != 3) return false;
+    if (v0.c_f32 || f0 != LEAN_PLAIN || (f1 | LEAN_OPTB) != LEAN_MULTI_F1) return false;
+    return tiles_of(v0, 64, 64) * v0.groups + tiles_of(v1, 64, 64) * v1.groups <= 256;
+}
+
+// The epilogue code (EPI) of a launch: the compact forms where they cover the parameter set, else the general one.
+int epilogue_form(const mmt_gemm_params& p) {
+    if (p.row_scale) return residual_epilogue(p, true) ? 2 : 0;
+    if (p.ln_fold != 1 && compact_epilogue(p)) return 1;  // (LayerNorm folded with handed-in statistics or none; conv too)
+    return p.conv_h == 0 && residual_epilogue(p) ? 2 : 0;
+}
+
+void set_tile(gemm_choice& c, int cfg, int nsk, int64_t wgs) {
+    const Cand& t = kCands[cfg - 1];
+    c.family = MMT_GEMM_LDS_DMA;
+    c.cfg = cfg, c.bm = t.bm, c.bn = t.bn, c.kgroups = t.ks, c.nsk = nsk;
+    c.wgs = (int32_t)wgs;
 }
 
 }  // namespace
 
-// Returns 1 when the shape / layout is not one this kernel takes (caller uses gemm.hip's kernel).
-template <typename T>
-int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
-    if (force < 0 || !glds_takes(p)) return 1;
-    // impl 10: gemm_glds_kernel where a lean frame kernel would run, at that kernel's tile shape and unsplit (A/B and
-    // the bitwise test of the lean kernels); every other parameter set as impl 0
+// ---- selection (host arithmetic only; nothing here launches)
+bool gemm_glds_select(const mmt_gemm_params& p, gemm_choice& out) {
+    if (p.impl < 0 || !glds_takes(p)) return false;
     const mmt_gemm_params pv = lean_view(p);
     int lform = 0;
     const int lcfg = lean_cfg(pv, &lform);
-    const bool no_lean = force == 10;
-    if (force == 10) force = lcfg;
-    const int nk = (p.K + 63) / 64;
-    const Cand* cands = kCands;
-    // largest split the workspace allows for a candidate (each slice keeps >= ks K-steps)
-    auto max_split = [&](const Cand& c) -> int {
-        if (p.ln_fold || !p.sk_ws || !p.sk_cnt) return 1;
-        const int64_t t = tiles_of(p, c.bm, c.bn) * p.groups;
-        if (2 * t > p.sk_cnt_n) return 1;  // a ticket and a published count per tile
-        int n = 8;
-        while (n > 1 && ((int64_t)n * c.ks > nk || t * n * c.bm * c.bn > p.sk_ws_floats)) --n;
-        return n;
-    };
-    auto cost = [&](const Cand& c, int n) {
-        const int64_t wg = tiles_of(p, c.bm, c.bn) * p.groups * n;
-        const int steps = (nk + n - 1) / n;
-        const float red = n > 1 ? 0.8f + 0.5f * (float)(n - 1) * (float)(c.bm * c.bn) / 16384.f : 0.f;
-        return (float)((wg + 255) / 256) * (c.fixed_us + (float)((steps + c.ks - 1) / c.ks) * c.step_us) + red;
-    };
-    int cfg = force, nsk = 1;
-    if (p.row_scale) {  // the training step's residual branches: impl 8's tile with the row-scale epilogue
-        if (force == 9) return launch_w4<T>(p, st);
-        if ((force != 0 && force != 8) || p.ln_fold || p.conv_h > 0 || p.a_t || p.w_t) return 1;
-        const dim3 grid((unsigned)tiles_of(p, 128, 128), 1, p.groups);
-        if (residual_epilogue(p, true))
-            hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, true, 2>), grid, dim3(512), 0, st, p);
-        else
-            hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, true>), grid, dim3(512), 0, st, p);
-        return 0;
-    }
-    if (p.a_t || p.w_t) {  // MN-major operands: the 128x128 tiles (impl 1, or impl 8 on big unsplit grids)
-        if (force != 0 && force != 1 && force != 8) return 1;
-        const int64_t t8 = tiles_of(p, 128, 128) * p.groups;
-        const bool big = t8 > 256;
-        const Cand& c = cands[0];
+    // impl 10: impl 0 with the lean kernels off -- where one would run, gemm_glds_kernel at that kernel's tile shape,
+    // unsplit (A/B and the bitwise test of the lean kernels)
+    const bool lean_off = p.impl == 10;
+    int cfg = lean_off ? lcfg : p.impl, nsk = 1;
+    const bool plain = p.conv_h == 0 && !p.a_t && !p.w_t;
+    gemm_choice c = out;
+    c.lnm = p.ln_fold;
+    if (p.row_scale) {  // the training step's residual branches: impl 8's tile (A/B: impl 9's) with the row-scale epilogue
+        if (cfg == 0) cfg = 8;
+        if ((cfg != 8 && cfg != 9) || p.ln_fold || !plain) return false;
+        c.rs = 1;
+    } else if (p.a_t || p.w_t) {  // MN-major operands: the 128x128 tiles (impl 1, or impl 8 on big unsplit grids)
+        if (cfg != 0 && cfg != 1 && cfg != 8) return false;
+        const Cand& c1 = kCands[0];
+        const int64_t t8 = tiles_of(p, c1) * p.groups;
         // Round 6: the weight gradients (A and W MN-major) of >= MMT_GEMM_SK8_MIN tiles on impl 8 with the K split
         // that fills ~480 of the 512 two-per-CU slots (the register hand-off above).  Isolated, two groups of 8448
         // tokens (profiles/r06_sk8_gemm_ab.jsonl): dW of qkv 104.1 -> 100.3 us (impl 1 unsplit -> 2 slices), proj
         // 49.7 -> 43.7 (impl 1 / 3 slices -> 6), fc1 144.6 -> 136.5 and fc2 134.8 -> 131.8 (impl 8 unsplit -> 2).
         // The input gradients (W only MN-major) stay unsplit: every split measured slower (dX of fc1 108.7 -> 133).
-        if (force == 0 && p.a_t && t8 >= MMT_GEMM_SK8_MIN && p.splitk == 0 && max_split(c) > 1) {
+        if (cfg == 0 && p.a_t && t8 >= MMT_GEMM_SK8_MIN && p.splitk == 0 && max_split(p, c1) > 1) {
             cfg = 8;
-            nsk = (int)std::min<int64_t>(max_split(c), (480 + t8 - 1) / t8);
-        } else if (force == 1 || (force == 0 && !big)) {
-            cfg = 1;
-            const int nmax = p.splitk >= 1 ? std::min(p.splitk, max_split(c)) : max_split(c);
+            nsk = (int)std::min<int64_t>(max_split(p, c1), (480 + t8 - 1) / t8);
+        } else if (cfg == 1 || (cfg == 0 && t8 <= 256)) {
             float best = 1e30f;
-            for (int n = (p.splitk >= 2 ? nmax : 1); n <= nmax; ++n) {
-                const float t = cost(c, n) * (n > 1 && p.splitk == 0 ? 1.15f : 1.f);
-                if (t < best) best = t, nsk = n;
-            }
+            try_cand(&p, 1, c1, true, best, cfg, nsk);
         } else {
             cfg = 8;
-            if (p.splitk >= 2) nsk = std::min(p.splitk, max_split(c));  // forced slice count (A/B tools)
+            if (p.splitk >= 2) nsk = std::min(p.splitk, max_split(p, c1));  // forced slice count (A/B tools)
         }
-        const int lnm = p.a_t ? 4 : 3;
-        const dim3 grid((unsigned)tiles_of(p, 128, 128), nsk, p.groups);
-        if (cfg == 8) {
-            if (lnm == 4) hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 4>), grid, dim3(512), 0, st, p);
-            else if (compact_epilogue(p)) hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 3, 1>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 3>), grid, dim3(512), 0, st, p);
-        } else {
-            if (lnm == 4) hipLaunchKernelGGL((gemm_glds_kernel<T, 128, 128, 2, 4, 1, 4, false, 4>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((gemm_glds_kernel<T, 128, 128, 2, 4, 1, 4, false, 3>), grid, dim3(512), 0, st, p);
-        }
-        return 0;
-    }
-    if (cfg == 0) {
+        c.lnm = p.a_t ? 4 : 3;
+    } else if (cfg == 0) {
         float best = 1e30f;
         // 128x256 (impl 6) only for grids of more than one round of 128x128 tiles: the batch-1 grids
         // (<= 240 tiles) keep their shapes; the large-M ones gain (gemm_ab.py: training dW 481-554 ->
@@ -1693,21 +1657,8 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
         // 256x256 (impl 7): plain GEMMs only (no folded LayerNorm, no conv, no split-K), and not under a
         // GELU epilogue, whose four-pass form measured slower (fc1 at 16 pairs: 515 vs 565 TFLOP/s)
         const bool big7 = big && !p.ln_fold && p.conv_h == 0 && p.act != 1;
-        for (int ci = 0; ci < (big7 ? 7 : big ? 6 : 3); ++ci) {
-            if (ci == 3 || ci == 4) continue;  // impl 4 / 5: A/B only
-            if (ci == 6) {  // impl 7: no split-K
-                const float t = cost(cands[ci], 1);
-                if (t < best) best = t, cfg = 7, nsk = 1;
-                continue;
-            }
-            const Cand& c = cands[ci];
-            const int nmax = p.splitk >= 1 ? std::min(p.splitk, max_split(c)) : max_split(c);
-            for (int n = (p.splitk >= 2 ? nmax : 1); n <= nmax; ++n) {
-                // a split must win clearly: the model prices the partial round trip loosely
-                const float t = cost(c, n) * (n > 1 && p.splitk == 0 ? 1.15f : 1.f);
-                if (t < best) best = t, cfg = c.cfg, nsk = n;
-            }
-        }
+        for (int ci = 0; ci < (big7 ? 7 : big ? 6 : 3); ++ci)
+            if (ci != 3 && ci != 4) try_cand(&p, 1, kCands[ci], ci != 6, best, cfg, nsk);  // impl 4 / 5: A/B only
         // 128x128 at two workgroups per CU (impl 8) instead of a one-per-CU 128x128 / 256x128 / 128x256 tile
         // on big unsplit plain grids: 1.14-1.25x impl 1 and 1.02-1.16x the model's pick on the training
         // step's forward / dX shapes and batch-8 fc1 / fc2 (profiles/r03_gemm_occ2_ab.jsonl); the
@@ -1727,72 +1678,162 @@ int mmt_gemm_glds(const mmt_gemm_params& p, hipStream_t st, int force) {
             (MMT_GEMM_OCC2_RES || !p.ln_stats_out[0]) &&
             (cfg == 1 || cfg == 5 || cfg == 6 || cfg == 7 || (p.ln_fold == 2 && (cfg == 2 || cfg == 3))))
             cfg = 8;
-    } else if (cfg == 8) {
-        nsk = 1;  // impl 8: no split-K
-    } else if (cfg >= 1 && cfg <= 7) {
-        const Cand& c = cands[cfg - 1];
-        if (no_lean) {
-            nsk = 1;
-        } else if (p.splitk >= 2) {
-            nsk = std::min(p.splitk, max_split(c));
-        } else if (p.splitk == 0) {
-            float best = 1e30f;
-            for (int n = 1; n <= max_split(c); ++n) {
-                const float t = cost(c, n) * (n > 1 ? 1.15f : 1.f);
-                if (t < best) best = t, nsk = n;
-            }
-        }
+    } else if (cfg >= 1 && cfg <= 7 && !lean_off) {  // a forced tile shape (impl 8 / 9: no split-K)
+        float best = 1e30f;
+        try_cand(&p, 1, kCands[cfg - 1], true, best, cfg, nsk);
     }
-    if (!no_lean && nsk == 1 && cfg != 0 && cfg == lcfg) {  // the tile shapes of cases 1 / 2 / 3 below
-        constexpr int PL = LEAN_PLAIN, PR = LEAN_PLAIN | LEAN_R, A2 = LEAN_A2;
-        if (cfg == 1 && p.act == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 1>(pv, st);
-        else if (cfg == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 0>(pv, st);
-        else if (cfg == 2) launch_lean<T, 128, 64, 2, 2, 2, 3, 0, 1, 2, PL>(pv, st);
-        else if (lform == 0) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0>(pv, st);
-        else if (!p.c_f32) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 1, 0, PL>(pv, st);
-        else if (lform == PL) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL>(pv, st);
-        else if (lform == PR) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR>(pv, st);
-        else if (lform == (PL | A2)) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL | A2>(pv, st);
-        else launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR | A2>(pv, st);
-        return 0;
-    }
-    switch (cfg) {
-        case 1: launch<T, 128, 128, 2, 4, 1, 4>(p, nsk, st); break;
-        case 2: launch<T, 128, 64, 2, 2, 2, 3>(p, nsk, st); break;
-        case 3: launch<T, 64, 64, 2, 2, 2, 4>(p, nsk, st); break;
-        case 4: launch<T, 128, 128, 2, 2, 1, 4>(p, nsk, st); break;
-        case 5: launch<T, 256, 128, 4, 2, 1, 3>(p, nsk, st); break;
-        case 6: launch<T, 128, 256, 2, 4, 1, 3>(p, nsk, st); break;
-        case 7:
-            if (p.ln_fold || p.conv_h > 0 || nsk > 1) return 1;
-            hipLaunchKernelGGL((gemm_glds_kernel<T, 256, 256, 4, 2, 1, 2, false, 0>),
-                               dim3((unsigned)tiles_of(p, 256, 256), 1, p.groups), dim3(512), 0, st, p);
-            break;
-        case 8:  // 128x128 at two workgroups per CU: plain GEMM mode (LayerNorm fold only with handed-in statistics, no
-                 // conv), and no split-K: its 64 KiB ring holds the fp32 tile image only in two passes (as impl 7)
-            if (p.ln_fold == 1 || p.conv_h > 0 || nsk > 1) return 1;
-            {
-                const dim3 grid((unsigned)tiles_of(p, 128, 128), nsk, p.groups);
-                if (p.ln_fold == 2) {
-                    if (compact_epilogue(p))
-                        hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, false, 1, 2>), grid, dim3(512), 0, st, p);
-                    else
-                        hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, false, 0, 2>), grid, dim3(512), 0, st, p);
-                } else if (compact_epilogue(p))
-                    hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, false, 1>), grid, dim3(512), 0, st, p);
-                else if (residual_epilogue(p))
-                    hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, false, 2>), grid, dim3(512), 0, st, p);
-                else
-                    hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2>), grid, dim3(512), 0, st, p);
-            }
-            break;
-        case 9: return launch_w4<T>(p, st);
-        default: return 1;
-    }
-    return 0;
+    if (cfg < 1 || cfg > 9 || (cfg == 9 && !MMT_GEMM_AB)) return false;
+    // impl 7 / 8 / 9: plain GEMM mode (impl 8 / 9 also the LayerNorm fold on handed-in statistics), and their rings do
+    // not hold the fp32 tile image a K split hands over (impl 8's MN-major forms split through registers)
+    if (cfg >= 7 && c.lnm < 3 && (p.conv_h > 0 || nsk > 1 || (cfg == 7 ? p.ln_fold != 0 : p.ln_fold == 1))) return false;
+    if (cfg == 9 && (p.a_t || p.w_t)) return false;
+    set_tile(c, cfg, nsk, tiles_of(p, kCands[cfg - 1]) * nsk * p.groups);
+    c.lean = !lean_off && nsk == 1 && cfg == lcfg;  // (lean_cfg: one of the tile shapes 1 / 2 / 3)
+    if (c.lean) c.form = lform, c.epi = cfg == 3 && p.c_f32 ? 2 : 1;
+    else if (c.lnm >= 3) c.epi = cfg == 8 && !p.a_t && compact_epilogue(p);  // MN-major: impl 8 with W alone
+    else if (cfg != 7) c.epi = epilogue_form(p);  // (impl 7: the general epilogue only)
+    out = c;
+    return true;
 }
 
+// The configuration is chosen once for the union: rounds of 256 workgroups over all problems times the slowest
+// problem's per-workgroup time (the cost model above).  impl 10: as 0, but never the lean multi kernel.
+bool gemm_glds_select_multi(const mmt_gemm_params* ps, int n, gemm_choice& c) {
+    if (n < 1 || n > GEMM_MULTI) return false;
+    const bool conv = ps[0].conv_h > 0, lean_off = ps[0].impl == 10;
+    int cfg = lean_off ? 0 : ps[0].impl, nsk = 1;
+    for (int i = 0; i < n; ++i) {
+        const mmt_gemm_params& p = ps[i];
+        if (!glds_takes(p) || (p.conv_h > 0) != conv || p.ln_fold || p.impl != ps[0].impl || cfg < 0 || cfg > 4 ||
+            p.a_t || p.w_t)
+            return false;
+    }
+    if (cfg == 0) {
+        float best = 1e30f;
+        for (int ci = 0; ci < 3; ++ci) try_cand(ps, n, kCands[ci], false, best, cfg, nsk);
+    }
+    int64_t wg_total = 0;
+    for (int i = 0; i < n; ++i) wg_total += tiles_of(ps[i], kCands[cfg - 1]) * ps[i].groups;
+    if (wg_total > INT32_MAX) return false;
+    set_tile(c, cfg, 1, wg_total);
+    c.conv = conv, c.joint = n;
+    c.lean = cfg == 3 && !conv && !lean_off && lean_multi(ps, n);
+    if (c.lean) c.form = LEAN_MULTI_F1;
+    return true;
+}
+
+// ---- launch: the only code that names the kernel instantiations
 namespace {
+
+#define MMT_V(x) decltype(x)::value
+
+// The general-kernel launches of one choice (everything but the lean and the joint kernels).
+struct glds_launcher {
+    const gemm_choice& c;
+
+    // The (LNM, EPI) ladder the tile families share: hands the form of the choice to f as compile-time values and
+    // returns true -- unless it is the plain general kernel (LNM 0, EPI 0), which is each family's own line.
+    template <typename F>
+    bool folded_or_compact(F&& f) const {
+        if (c.lnm == 2) c.epi == 1 ? f(gemm_ic<2>{}, gemm_ic<1>{}) : f(gemm_ic<2>{}, gemm_ic<0>{});
+        else if (c.epi == 1) f(gemm_ic<0>{}, gemm_ic<1>{});
+        else if (c.epi == 2) f(gemm_ic<0>{}, gemm_ic<2>{});
+        else return false;
+        return true;
+    }
+    // The row-scale kernels' two forms: residual producer or general.
+    template <typename F>
+    void rs_forms(F&& f) const {
+        c.epi == 2 ? f(gemm_ic<2>{}) : f(gemm_ic<0>{});
+    }
+
+    // impl 1 .. 6: GEMM mode in every plain form and with the LayerNorm statistics summed in the K loop; conv mode
+    template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST>
+    void launch(const mmt_gemm_params& p, int nsk, hipStream_t st) const {
+        const dim3 grid(c.wgs / (nsk * p.groups), nsk, p.groups), block(64 * WGM * WGN * KS);
+        if (c.conv && c.epi)  // the corner head's plain conv + ReLU layers
+            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, true, 0, 1>), grid, block, 0, st, p);
+        else if (c.conv)
+            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, true, 0>), grid, block, 0, st, p);
+        else if (c.lnm == 1)
+            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 1>), grid, block, 0, st, p);
+        else if (!folded_or_compact([&](auto lnm, auto epi) {
+                     hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, MMT_V(lnm), MMT_V(epi)>),
+                                        grid, block, 0, st, p);
+                 }))
+            hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WGM, WGN, KS, ST, false, 0>), grid, block, 0, st, p);
+    }
+
+    // impl 8: the two-per-CU tile, with the row scale, MN-major operands or the plain forms
+    template <typename T>
+    void launch_occ2(const mmt_gemm_params& p, int nsk, hipStream_t st) const {
+        const dim3 grid(c.wgs / (nsk * p.groups), nsk, p.groups), block(512);
+        if (c.rs)
+            rs_forms([&](auto epi) {
+                hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, true, MMT_V(epi)>), grid, block, 0, st, p);
+            });
+        else if (c.lnm == 4) hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 4>), grid, block, 0, st, p);
+        else if (c.lnm == 3 && c.epi) hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 3, 1>), grid, block, 0, st, p);
+        else if (c.lnm == 3) hipLaunchKernelGGL((gemm_glds_kernel_occ2_t<T, 3>), grid, block, 0, st, p);
+        else if (!folded_or_compact([&](auto lnm, auto epi) {
+                     hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2, false, MMT_V(epi), MMT_V(lnm)>), grid,
+                                        block, 0, st, p);
+                 }))
+            hipLaunchKernelGGL((gemm_glds_kernel_occ2<T, 128, 128, 2, 4, 1, 2>), grid, block, 0, st, p);
+    }
+
+    // impl 9 (A/B builds): the row scale or the plain forms
+    template <typename T>
+    void launch_w4(const mmt_gemm_params& p, hipStream_t st) const {
+#if MMT_GEMM_AB
+        const dim3 grid(c.wgs / p.groups, 1, p.groups), block(256);
+        if (c.rs)
+            rs_forms([&](auto epi) {
+                hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0, true, MMT_V(epi)>), grid, block, 0, st, p);
+            });
+        else if (!folded_or_compact([&](auto lnm, auto epi) {
+                     hipLaunchKernelGGL((gemm_glds_kernel_w4<T, MMT_V(lnm), false, MMT_V(epi)>), grid, block, 0, st, p);
+                 }))
+            hipLaunchKernelGGL((gemm_glds_kernel_w4<T, 0>), grid, block, 0, st, p);
+#endif
+    }
+
+    template <typename T>
+    void run(const mmt_gemm_params& p, hipStream_t st) const {
+        const int nsk = c.nsk;
+        if (c.cfg == 1 && c.lnm >= 3) {  // MN-major operands on the one-per-CU 128x128 tile
+            const dim3 grid(c.wgs / (nsk * p.groups), nsk, p.groups);
+            if (c.lnm == 4) hipLaunchKernelGGL((gemm_glds_kernel<T, 128, 128, 2, 4, 1, 4, false, 4>), grid, dim3(512), 0, st, p);
+            else hipLaunchKernelGGL((gemm_glds_kernel<T, 128, 128, 2, 4, 1, 4, false, 3>), grid, dim3(512), 0, st, p);
+            return;
+        }
+        switch (c.cfg) {
+            case 1: launch<T, 128, 128, 2, 4, 1, 4>(p, nsk, st); break;
+            case 2: launch<T, 128, 64, 2, 2, 2, 3>(p, nsk, st); break;
+            case 3: launch<T, 64, 64, 2, 2, 2, 4>(p, nsk, st); break;
+            case 4: launch<T, 128, 128, 2, 2, 1, 4>(p, nsk, st); break;
+            case 5: launch<T, 256, 128, 4, 2, 1, 3>(p, nsk, st); break;
+            case 6: launch<T, 128, 256, 2, 4, 1, 3>(p, nsk, st); break;
+            case 7:
+                hipLaunchKernelGGL((gemm_glds_kernel<T, 256, 256, 4, 2, 1, 2, false, 0>),
+                                   dim3(c.wgs / p.groups, 1, p.groups), dim3(512), 0, st, p);
+                break;
+            case 8: launch_occ2<T>(p, nsk, st); break;
+            default: launch_w4<T>(p, st); break;
+        }
+    }
+};
+#undef MMT_V
+
+template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST, int LNM, int EPI, int ACT, int FORM = 0>
+void launch_lean(const mmt_gemm_params& p, hipStream_t st) {
+    gemm_lean_args<EPI, ACT, FORM> a{};
+    const int nwg = (int)tiles_of(p, BM, BN) * p.groups;
+    fill_lean<BM, BN>(a, p, nwg);
+    hipLaunchKernelGGL((gemm_glds_frame_kernel<T, BM, BN, WGM, WGN, KS, ST, LNM, EPI, ACT, FORM>), dim3(nwg),
+                       dim3(64 * WGM * WGN * KS), 0, st, a);
+}
+
 template <typename T, int BM, int BN, int WGM, int WGN, int KS, int ST>
 void launch_multi(const mmt_gemm_params* ps, int n, bool conv, hipStream_t st) {
     gemm_multi_args a{};
@@ -1808,80 +1849,47 @@ void launch_multi(const mmt_gemm_params* ps, int n, bool conv, hipStream_t st) {
     else hipLaunchKernelGGL((gemm_glds_multi_kernel<T, BM, BN, WGM, WGN, KS, ST, false>), grid, block, 0, st, a);
 }
 
-// The lean multi launch (gemm_glds_frame_multi_kernel) of the pair the frame's fusion encoder issues, at the 64x64
-// tile the cost model picks for it: a 16-bit C = acc + bias (the value Linear) beside an fp32 C = acc (+ bias) + R
-// with A from two pointers (the offsets Linear) -- every problem a lean form, the union one round.  false: not that.
 template <typename T>
-bool launch_lean_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
-    constexpr int BM = 64, BN = 64, F1 = LEAN_PLAIN | LEAN_R | LEAN_A2 | LEAN_OPTB;
+void launch_lean_multi(const mmt_gemm_params* ps, const gemm_choice& c, hipStream_t st) {
+    constexpr int BM = 64, BN = 64;
     using P0 = gemm_lean_args<1, 0, LEAN_PLAIN>;
-    using P1 = gemm_lean_args<2, 0, F1>;
-    if (n != 2) return false;
+    using P1 = gemm_lean_args<2, 0, LEAN_MULTI_F1>;
     const mmt_gemm_params v0 = lean_view(ps[0]), v1 = lean_view(ps[1]);
-    int f0 = 0, f1 = 0;
-    if (lean_cfg(v0, &f0, true) != 3 || lean_cfg(v1, &f1, true) != 3) return false;
-    if (v0.c_f32 || f0 != LEAN_PLAIN || (f1 | LEAN_OPTB) != F1) return false;
-    const int wg0 = (int)tiles_of(v0, BM, BN) * v0.groups, wg1 = (int)tiles_of(v1, BM, BN) * v1.groups;
-    if (wg0 + wg1 > 256) return false;
     gemm_lean_multi_args<P0, P1> a{};
-    fill_lean<BM, BN>(a.p0, v0, wg0 + wg1);
-    fill_lean<BM, BN>(a.p1, v1, wg0 + wg1);
-    a.wg1 = wg0;
-    a.q8 = (wg0 + wg1) >> 3;
-    a.r8 = (wg0 + wg1) & 7;
-    hipLaunchKernelGGL((gemm_glds_frame_multi_kernel<T, BM, BN, 2, 2, 2, 4, 1, P0, 2, P1>), dim3(wg0 + wg1), dim3(512),
-                       0, st, a);
-    return true;
+    fill_lean<BM, BN>(a.p0, v0, c.wgs);
+    fill_lean<BM, BN>(a.p1, v1, c.wgs);
+    a.wg1 = (int)tiles_of(v0, BM, BN) * v0.groups;
+    a.q8 = c.wgs >> 3;
+    a.r8 = c.wgs & 7;
+    hipLaunchKernelGGL((gemm_glds_frame_multi_kernel<T, BM, BN, 2, 2, 2, 4, 1, P0, 2, P1>), dim3(c.wgs), dim3(512), 0, st, a);
 }
+
 }  // namespace
 
-// n independent GEMMs in one launch; returns 1 when some problem is not one the LDS-DMA kernel
-// takes in this mode (all GEMM or all conv, no folded LayerNorm, no split-K, one forced impl).  The
-// configuration is chosen once for the union: rounds of 256 workgroups over all problems times the
-// slowest problem's per-workgroup time (the cost model above).  impl 10: as 0, but never the lean multi kernel.
 template <typename T>
-int mmt_gemm_glds_multi(const mmt_gemm_params* ps, int n, hipStream_t st) {
-    if (n < 1 || n > GEMM_MULTI) return 1;
-    const bool conv = ps[0].conv_h > 0;
-    const bool no_lean = ps[0].impl == 10;
-    const int force = no_lean ? 0 : ps[0].impl;
-    for (int i = 0; i < n; ++i) {
-        const mmt_gemm_params& p = ps[i];
-        if (!glds_takes(p) || (p.conv_h > 0) != conv || p.ln_fold || p.impl != ps[0].impl || force < 0 || force > 4 ||
-            p.a_t || p.w_t)
-            return 1;
+void gemm_glds_launch(const mmt_gemm_params* ps, const gemm_choice& c, hipStream_t st) {
+    const mmt_gemm_params& p = ps[0];
+    if (c.joint || c.lean) {
+        constexpr int PL = LEAN_PLAIN, PR = LEAN_PLAIN | LEAN_R, A2 = LEAN_A2;
+        const mmt_gemm_params pv = lean_view(p);  // the lean argument blocks read this view
+        if (c.joint && c.lean) launch_lean_multi<T>(ps, c, st);
+        else if (c.joint && c.cfg == 1) launch_multi<T, 128, 128, 2, 4, 1, 4>(ps, c.joint, c.conv, st);
+        else if (c.joint && c.cfg == 2) launch_multi<T, 128, 64, 2, 2, 2, 3>(ps, c.joint, c.conv, st);
+        else if (c.joint && c.cfg == 3) launch_multi<T, 64, 64, 2, 2, 2, 4>(ps, c.joint, c.conv, st);
+        else if (c.joint) launch_multi<T, 128, 128, 2, 2, 1, 4>(ps, c.joint, c.conv, st);
+        else if (c.cfg == 1 && p.act == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 1>(pv, st);
+        else if (c.cfg == 1) launch_lean<T, 128, 128, 2, 4, 1, 4, 2, 1, 0>(pv, st);
+        else if (c.cfg == 2) launch_lean<T, 128, 64, 2, 2, 2, 3, 0, 1, 2, PL>(pv, st);
+        else if (c.form == 0) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0>(pv, st);
+        else if (c.epi == 1) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 1, 0, PL>(pv, st);
+        else if (c.form == PL) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL>(pv, st);
+        else if (c.form == PR) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR>(pv, st);
+        else if (c.form == (PL | A2)) launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PL | A2>(pv, st);
+        else launch_lean<T, 64, 64, 2, 2, 2, 4, 0, 2, 0, PR | A2>(pv, st);
+        return;
     }
-    int cfg = force;
-    if (cfg == 0) {
-        float best = 1e30f;
-        for (int ci = 0; ci < 3; ++ci) {
-            const Cand& c = kCands[ci];
-            int64_t wg = 0;
-            float slowest = 0.f;
-            for (int i = 0; i < n; ++i) {
-                wg += tiles_of(ps[i], c.bm, c.bn) * ps[i].groups;
-                const int steps = (ps[i].K + 63) / 64;
-                slowest = std::max(slowest, c.fixed_us + (float)((steps + c.ks - 1) / c.ks) * c.step_us);
-            }
-            const float t = (float)((wg + 255) / 256) * slowest;
-            if (t < best) best = t, cfg = c.cfg;
-        }
-    }
-    int64_t wg_total = 0;
-    for (int i = 0; i < n; ++i) wg_total += tiles_of(ps[i], kCands[cfg - 1].bm, kCands[cfg - 1].bn) * ps[i].groups;
-    if (wg_total > INT32_MAX) return 1;
-    if (cfg == 3 && !conv && !no_lean && launch_lean_multi<T>(ps, n, st)) return 0;
-    switch (cfg) {
-        case 1: launch_multi<T, 128, 128, 2, 4, 1, 4>(ps, n, conv, st); break;
-        case 2: launch_multi<T, 128, 64, 2, 2, 2, 3>(ps, n, conv, st); break;
-        case 3: launch_multi<T, 64, 64, 2, 2, 2, 4>(ps, n, conv, st); break;
-        case 4: launch_multi<T, 128, 128, 2, 2, 1, 4>(ps, n, conv, st); break;
-        default: return 1;
-    }
-    return 0;
+    glds_launcher{c}.run<T>(p, st);
 }
 
-template int mmt_gemm_glds<bf16_t>(const mmt_gemm_params&, hipStream_t, int);
-template int mmt_gemm_glds<f16_t>(const mmt_gemm_params&, hipStream_t, int);
-template int mmt_gemm_glds_multi<bf16_t>(const mmt_gemm_params*, int, hipStream_t);
-template int mmt_gemm_glds_multi<f16_t>(const mmt_gemm_params*, int, hipStream_t);
+template void gemm_glds_launch<bf16_t>(const mmt_gemm_params*, const gemm_choice&, hipStream_t);
+template void gemm_glds_launch<f16_t>(const mmt_gemm_params*, const gemm_choice&, hipStream_t);

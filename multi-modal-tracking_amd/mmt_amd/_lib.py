@@ -41,6 +41,15 @@ class GemmParams(ctypes.Structure):
     ]
 
 
+class GemmChoice(ctypes.Structure):
+    """mmt_gemm_choice: what mmt_gemm_select answers."""
+    _fields_ = [(f, i32) for f in ("family", "bm", "bn", "kgroups", "cfg", "nsk", "epi", "lnm", "rs", "conv", "lean",
+                                   "form", "joint", "wgs")]
+
+
+GEMM_REJECTED, GEMM_GEMV, GEMM_REG_TILE, GEMM_LDS_DMA, GEMM_SEPARATELY = range(5)
+
+
 class AttnParams(ctypes.Structure):
     _fields_ = [("qkv", vp), ("out", vp), ("S", i32), ("Bm", i32), ("ntok", i32), ("n_t", i32), ("C", i32),
                 ("H", i32), ("asym", i32), ("scale", f32), ("impl", i32), ("lse", vp), ("q_part", i32),
@@ -78,6 +87,7 @@ WPREP_MAX = 24
 _PROTOS = {
     "mmt_gemm": [ctypes.POINTER(GemmParams), i32, vp],
     "mmt_gemm_multi": [ctypes.POINTER(GemmParams), i32, i32, vp],
+    "mmt_gemm_select": [ctypes.POINTER(GemmParams), i32, i32, ctypes.POINTER(GemmChoice)],
     "mmt_mam_attention": [ctypes.POINTER(AttnParams), i32, vp],
     "mmt_mam_attention_bwd": [ctypes.POINTER(AttnBwdParams), i32, vp],
     "mmt_transpose_bf16": [vp, vp, i32, i32, i64, i64, i32, i64, i64, i32, vp],
@@ -173,6 +183,14 @@ def _load():
 
 LIB = _load()
 EXPORTED = tuple(_PROTOS) + ("mmt_version",)
+
+
+def gemm_select(params, dtype, n=1):
+    """The kernel mmt_gemm (n == 1: params one GemmParams) or mmt_gemm_multi (an array of n) would run: a GemmChoice,
+    or None where the call would be rejected.  Host arithmetic only."""
+    out = GemmChoice()
+    status = LIB.mmt_gemm_select(params if n > 1 else ctypes.byref(params), n, dtype, ctypes.byref(out))
+    return out if status == 0 else None
 
 
 class MMTError(RuntimeError):

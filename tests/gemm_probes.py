@@ -19,15 +19,13 @@ contract; it lies inside the allocation (an over-read faults nothing) and turns 
 and same() compares all of it: every element written with the right value, no guard element touched, no
 NaN read into the region.
 
-TILES is the geometry of mmt_gemm_glds's switch (BM, BN, k-groups KS, ring slots ST; K-step 64);
+TILES is the geometry of the launch switch of gemm_glds.hip (BM, BN, k-groups KS, ring slots ST; K-step 64);
 the register-staged kernel (impl -1 and all fp32) runs 64x64 tiles with one k-group below 8 K-steps and
 two from 8 on, 128x128 tiles from 512 of them up, behind a ring of 3 register stages; its K-step is 64
 (16-bit) or 32 (fp32) elements.
 
-kernel_of() / takes() / split_used() mirror check_gemm, glds_takes, the switch's per-impl restrictions and
-max_split: a forced impl the LDS-DMA dispatcher declines falls back silently to the register-staged kernel
-and a forced splitk is clipped silently, so a probe that wants impl 7 or five slices proves with them that
-it does not end up testing something else.
+kernel_of() / takes() / split_used() / grid_of() / epilogue_path() read the library's own answer (mmt_gemm_select on
+params_of(spec), no GPU needed), so a probe that wants impl 7 or five slices proves that it gets them.
 """
 import dataclasses
 import functools
@@ -101,11 +99,7 @@ def tile_of(impl, dname="bf16"):
     return TILES[3] if impl == 0 else TILES[impl]
 
 
-# ------------------------------------------------------------------------------------------------ dispatch mirror
-def _tiles(M, N, bm, bn):
-    return ((M + bm - 1) // bm) * ((N + bn - 1) // bn)
-
-
+# ------------------------------------------------------------------------------------------------ storage geometry
 def geometry(s):
     """Strides of the poisoned storage of a spec (elements): what the launch passes."""
     g = {"ldc": s.N + PAD, "ldr": s.N + PAD, "ldw": s.N + PAD if s.w_t else 0}
@@ -170,189 +164,76 @@ def r_phys_rows(s):
     return c_phys_rows(s)
 
 
-def valid(s):
-    """check_gemm: the launch is accepted at all."""
-    epc = 16 // esize(s.dtype)
-    g = geometry(s)
-    if s.M <= 0 or s.N <= 0 or s.K <= 0 or not 1 <= s.groups <= 2 or not -1 <= s.impl <= 9:
-        return False
-    if s.act not in (0, 1, 2, 5) or not 0 <= s.c2_copy <= 4 or (s.c2_copy == 4 and not s.c_f32):
-        return False
-    if s.K % epc or g["lda"] % epc:
-        return False
+# ------------------------------------------------------------------------------------------------ dispatch (the library's)
+def _lib():
+    from mmt_amd import _lib
+    return _lib
+
+
+def dtype_code(dname):
+    L = _lib()
+    return {"f32": L.MMT_F32, "bf16": L.MMT_BF16, "fp16": L.MMT_F16}[dname]
+
+
+_FAKE = 1 << 20  # stands for every buffer when the library is only asked: non-null, 16-B aligned, never dereferenced
+
+
+def params_of(s, ptrs=None):
+    """mmt_gemm_params of a spec.  ptrs: name -> device addresses (per group: a, w, c, bias, r, c2, a1, stats, colsum,
+    stats_in; row_scale; sk = (slabs, tickets)); without it every buffer the spec has is a fake address, which is
+    all the selection looks at.  The split-K workspace is handed in with a forced split only."""
+    L, geo = _lib(), geometry(s)
+    at = (lambda name, q: _FAKE) if ptrs is None else (lambda name, q: ptrs[name][q])
+    p = L.GemmParams()
+    for q in range(s.groups):
+        p.a[q], p.w[q], p.c[q] = at("a", q), at("w", q), at("c", q)
+        p.bias[q] = at("bias", q) if s.bias else None
+        p.r[q] = at("r", q) if s.r else None
+        p.c2[q] = at("c2", q) if s.c2 else None
+        p.a1[q] = at("a1", q) if s.k_split else None
+        p.ln_stats_out[q] = at("stats", q) if s.stats else None
+        p.ln_colsum[q] = at("colsum", q) if s.ln_fold else None
+        p.ln_stats_in[q] = at("stats_in", q) if s.ln_fold == 2 else None
+    p.lda, p.ldc, p.ldr = geo["lda"], geo["ldc"], geo["ldr"]
+    p.a_seg_rows, p.a_segs_a, p.a_stride_a, p.a_stride_b = geo["seg"]
+    p.M, p.N, p.K, p.k_split = s.M, s.N, s.K, s.k_split
+    p.act, p.c_f32, p.c2_copy, p.groups, p.impl = s.act, s.c_f32, s.c2_copy, s.groups, s.impl
+    p.r_mode, p.r_p0, p.r_p1, p.r_t = s.r_mode, s.r_p0, s.r_p1, int(s.r == 2)
     if s.conv:
-        h, up, cin, k3, _ = s.conv
-        if cin % epc or up < 1 or h % up or k3 not in (0, 1, 2) or s.K != (9 if k3 else 1) * cin or s.M % (h * h):
-            return False
-    elif s.k_split % epc:
-        return False
-    if s.a_t and not s.w_t:
-        return False
-    if s.w_t:
-        if s.dtype == "f32" or s.conv or s.ln_fold or s.k_split or s.a_seg or s.N % 8:
-            return False
-        if s.a_t and s.M % 8:
-            return False
-    if s.r_mode == 2 and (s.r_p1 < 1 or s.r_p0 % s.r_p1):
-        return False
-    if s.r_mode == 1 and s.r_p0 < 1:
-        return False
-    if s.c_seg and (s.conv or s.c_seg[1] < s.c_seg[0]):
-        return False
-    if s.c2 and not s.r and s.c2_copy < 2:
-        return False
-    if (s.act == 5 and not s.r) or (s.c2_copy >= 2 and not s.c2):
-        return False
-    if s.c2_copy >= 3 and s.N % 8:
-        return False
-    return True
-
-
-def glds_takes(s):
-    """glds_takes: a shape / layout of the LDS-DMA kernels (pointers: the storage here is 16-B aligned)."""
-    g = geometry(s)
-    if s.dtype == "f32" or s.K % 8 or s.N % 8 or g["ldc"] % 8 or (s.r and g["ldr"] % 8):
-        return False
-    if s.ln_fold and s.conv:
-        return False
-    if s.ln_fold == 2 and (s.a_seg or s.k_split or s.K % 64 or s.K > 1024):
-        return False
-    if s.stats and (not s.c2_copy or not s.c2 or s.N % 64):
-        return False
-    if s.conv:
-        h, up = s.conv[0], s.conv[1]
-        if up <= 0 or up & (up - 1) or (h // up) * up != h:
-            return False
-    if g["lda"] % 8 or g["seg"][2] % 8 or g["seg"][3] % 8 or s.k_split % 8:
-        return False
-    return True
-
-
-def epilogue_path(s):
-    """Which epilogue code of the LDS-DMA kernels a spec runs: 0 general, 1 compact 16-bit, 2 residual producer."""
-    compact = not (s.c_f32 or s.c2_copy not in (0, 2) or (s.c_seg and s.c2_copy == 2) or s.row_scale_div or
-                   s.act not in (0, 1, 2) or s.r or s.stats or s.c2 != (s.c2_copy == 2))
-    resid = bool(s.c_f32 and not s.act and not s.c_seg and not s.r_mode and s.r != 2 and not s.ln_fold and
-                 (s.c2_copy == 1 if s.c2 else not (s.c2_copy or s.stats)))
-    if s.row_scale_div or s.a_t:
-        return 2 if resid and not s.a_t else 0
-    if s.w_t:
-        return 1 if compact and _resolve(s)[0] == 8 else 0
-    if s.conv:
-        return 1 if compact else 0
-    if s.ln_fold != 1 and compact:
-        return 1
-    return 2 if resid else 0
-
-
-def max_split(s, impl):
-    bm, bn, ks, _ = TILES[impl]
-    nk = (s.K + 63) // 64
-    if s.ln_fold or not s.splitk or not s.ws_floats or not s.cnt_n:  # (the tests hand the buffers in with a forced split only)
-        return 1
-    t = _tiles(s.M, s.N, bm, bn) * s.groups
-    if 2 * t > s.cnt_n:
-        return 1
-    n = 8
-    while n > 1 and (n * ks > nk or t * n * bm * bn > s.ws_floats):
-        n -= 1
-    return n
-
-
-_COST = {1: (6.0, 0.52), 2: (5.0, 0.52), 3: (3.2, 0.33), 4: (6.0, 0.60), 5: (7.0, 0.70), 6: (7.0, 0.70), 7: (9.0, 1.33)}
-
-
-def _cost(s, impl, n):
-    bm, bn, ks, _ = TILES[impl]
-    fixed, step = _COST[impl]
-    nk = (s.K + 63) // 64
-    wg = _tiles(s.M, s.N, bm, bn) * s.groups * n
-    steps = (nk + n - 1) // n
-    red = 0.8 + 0.5 * (n - 1) * (bm * bn) / 16384.0 if n > 1 else 0.0
-    return ((wg + 255) // 256) * (fixed + ((steps + ks - 1) // ks) * step) + red
-
-
-def _resolve(s):
-    """mmt_gemm_glds: (tile configuration, K slices) of a spec the LDS-DMA kernels take, or None (falls back)."""
-    force = s.impl
-    sk = s.splitk if s.ws_floats and s.cnt_n else 0
-    if force < 0 or not glds_takes(s):
-        return None
+        p.conv_h, p.conv_up, p.conv_cin, p.conv_k3 = s.conv[:4]
+    if s.splitk:
+        p.splitk, p.sk_ws_floats, p.sk_cnt_n = s.splitk, s.ws_floats, s.cnt_n
+        p.sk_ws, p.sk_cnt = at("sk", 0), at("sk", 1)
+    if s.c_seg:
+        p.c_seg_rows, p.c_seg_pitch = s.c_seg
+    p.a_t, p.w_t, p.ldw = s.a_t, s.w_t, geo["ldw"]
     if s.row_scale_div:
-        if force not in (0, 8) or s.ln_fold or s.conv or s.a_t or s.w_t:
-            return None
-        return 8, 1
-    if s.a_t or s.w_t:
-        if force not in (0, 1, 8):
-            return None
-        t8 = _tiles(s.M, s.N, 128, 128) * s.groups
-        if force == 0 and s.a_t and t8 >= 64 and s.splitk == 0 and max_split(s, 1) > 1:
-            return 8, min(max_split(s, 1), (480 + t8 - 1) // t8)
-        if force == 1 or (force == 0 and t8 <= 256):
-            nmax = min(s.splitk, max_split(s, 1)) if s.splitk >= 1 else max_split(s, 1)
-            best, nsk = 1e30, 1
-            for n in range(nmax if s.splitk >= 2 else 1, nmax + 1):
-                t = _cost(s, 1, n) * (1.15 if n > 1 and s.splitk == 0 else 1.0)
-                if t < best:
-                    best, nsk = t, n
-            return 1, nsk
-        return 8, (min(s.splitk, max_split(s, 1)) if s.splitk >= 2 else 1)
-    cfg, nsk = force, 1
-    if cfg == 0:
-        big = _tiles(s.M, s.N, 128, 128) * s.groups > 256
-        big7 = big and not s.ln_fold and not s.conv and s.act != 1
-        best = 1e30
-        for c in (1, 2, 3) + ((6,) if big else ()) + ((7,) if big7 else ()):
-            if c == 7:
-                t = _cost(s, 7, 1)
-                if t < best:
-                    best, cfg, nsk = t, 7, 1
-                continue
-            nmax = min(s.splitk, max_split(s, c)) if s.splitk >= 1 else max_split(s, c)
-            for n in range(nmax if s.splitk >= 2 else 1, nmax + 1):
-                t = _cost(s, c, n) * (1.15 if n > 1 and s.splitk == 0 else 1.0)
-                if t < best:
-                    best, cfg, nsk = t, c, n
-        if big and nsk == 1 and s.ln_fold != 1 and not s.conv and (cfg in (1, 5, 6, 7) or (s.ln_fold == 2 and cfg in (2, 3))):
-            cfg = 8
-    elif cfg == 8:
-        nsk = 1
-    elif 1 <= cfg <= 7:
-        if s.splitk >= 2:
-            nsk = min(s.splitk, max_split(s, cfg))
-        elif s.splitk == 0:
-            best = 1e30
-            for n in range(1, max_split(s, cfg) + 1):
-                t = _cost(s, cfg, n) * (1.15 if n > 1 else 1.0)
-                if t < best:
-                    best, nsk = t, n
-    else:
-        return None
-    if cfg == 7 and (s.ln_fold or s.conv or nsk > 1):
-        return None
-    if cfg == 8 and (s.ln_fold == 1 or s.conv or nsk > 1):
-        return None
-    return cfg, nsk
+        p.row_scale, p.row_scale_div = at("row_scale", 0), s.row_scale_div
+    if s.ln_fold:
+        p.ln_fold, p.ln_eps = s.ln_fold, LN_EPS
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+def select(s):
+    """mmt_gemm_select's answer for a spec (a GemmChoice), None when mmt_gemm rejects it."""
+    return _lib().gemm_select(params_of(s), dtype_code(s.dtype))
 
 
 def kernel_of(s):
     """The kernel a launch ends up in: ("glds", tile configuration, K slices), ("reg", BM, k-groups),
     ("gemv",) or None when mmt_gemm rejects it."""
-    if not valid(s):
+    c, L = select(s), _lib()
+    if c is None:
         return None
-    if (s.dtype == "f32" and s.M <= 16 and s.groups == 1 and not s.conv and not s.r and not s.c2 and s.c_f32 and
-            not s.k_split and not s.ln_fold and not s.splitk and not s.c_seg and not s.a_seg and s.impl <= 0):
+    if c.family == L.GEMM_GEMV:
         return ("gemv",)
-    if s.dtype != "f32":
-        r = _resolve(s)
-        if r:
-            return ("glds",) + r
-    if s.ln_fold or s.c2_copy or s.act == 5 or s.w_t or s.row_scale_div:
-        return None
-    nk = (s.K + kstep(s.dtype) - 1) // kstep(s.dtype)
-    if _tiles(s.M, s.N, 128, 128) * s.groups >= REG_BIG_TILES:
-        return ("reg", 128, 1)
-    return ("reg", 64, 2 if nk >= REG_KG2_STEPS else 1)
+    return ("glds", c.cfg, c.nsk) if c.family == L.GEMM_LDS_DMA else ("reg", c.bm, c.kgroups)
+
+
+def epilogue_path(s):
+    """Which epilogue code of the LDS-DMA kernels a spec runs: 0 general, 1 compact 16-bit, 2 residual producer."""
+    return select(s).epi
 
 
 def takes(impl, s):
@@ -374,11 +255,8 @@ def split_used(impl, s):
 
 def grid_of(s):
     """(workgroups, tiles_m) of the launch."""
-    k = kernel_of(s)
-    if k[0] == "glds":
-        bm, bn = TILES[k[1]][:2]
-        return _tiles(s.M, s.N, bm, bn) * k[2] * s.groups, (s.M + bm - 1) // bm
-    return _tiles(s.M, s.N, k[1], k[1]) * s.groups, (s.M + k[1] - 1) // k[1]
+    c = select(s)
+    return c.wgs, (s.M + c.bm - 1) // c.bm
 
 
 # ------------------------------------------------------------------------------------------------ shape lists
@@ -561,10 +439,14 @@ def multi_cases(mode, impl, n):
 
 
 def multi_one_launch(specs):
-    """mmt_gemm_glds_multi takes the problems in one launch."""
-    conv = bool(specs[0].conv)
-    return all(glds_takes(s) and bool(s.conv) == conv and not s.ln_fold and s.impl == specs[0].impl and
-               0 <= s.impl <= 4 and not s.a_t and not s.w_t and valid(s) for s in specs)
+    """mmt_gemm_multi takes the problems in one launch (mmt_gemm_select's answer for the array; it answers for
+    mmt_gemm when asked about one problem, so for a single spec: an LDS-DMA kernel takes it)."""
+    L = _lib()
+    if len(specs) == 1:
+        return kernel_of(specs[0])[0] == "glds"
+    arr = (L.GemmParams * len(specs))(*[params_of(s) for s in specs])
+    c = L.gemm_select(arr, dtype_code(specs[0].dtype), len(specs))
+    return c is not None and c.family == L.GEMM_LDS_DMA and c.joint == len(specs)
 
 
 LN_IMPLS = {1: (0, 1, 2, 3, 4, 5, 6), 2: (0, 1, 2, 3, 4, 5, 6, 8)}

@@ -36,10 +36,12 @@ def test_struct_layouts_match_header(tmp_path):
     from mmt_amd import _lib
     fields = [f for f, _ in _lib.GemmParams._fields_]
     afields = [f for f, _ in _lib.AttnParams._fields_]
+    cfields = [f for f, _ in _lib.GemmChoice._fields_]
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, "int main(void){",
-           'printf("%zu %zu\\n", sizeof(mmt_gemm_params), sizeof(mmt_attn_params));']
+           'printf("%zu %zu %zu\\n", sizeof(mmt_gemm_params), sizeof(mmt_attn_params), sizeof(mmt_gemm_choice));']
     src += ['printf("%%zu\\n", offsetof(mmt_gemm_params, %s));' % f for f in fields]
     src += ['printf("%%zu\\n", offsetof(mmt_attn_params, %s));' % f for f in afields]
+    src += ['printf("%%zu\\n", offsetof(mmt_gemm_choice, %s));' % f for f in cfields]
     src += ["return 0;}"]
     c = tmp_path / "abi.c"
     c.write_text("\n".join(src))
@@ -48,9 +50,82 @@ def test_struct_layouts_match_header(tmp_path):
     out = subprocess.check_output([str(exe)]).decode().split()
     assert int(out[0]) == ctypes.sizeof(_lib.GemmParams)
     assert int(out[1]) == ctypes.sizeof(_lib.AttnParams)
-    offs = [int(x) for x in out[2:]]
+    assert int(out[2]) == ctypes.sizeof(_lib.GemmChoice)
+    offs = [int(x) for x in out[3:]]
     assert offs[:len(fields)] == [getattr(_lib.GemmParams, f).offset for f in fields]
-    assert offs[len(fields):] == [getattr(_lib.AttnParams, f).offset for f in afields]
+    assert offs[len(fields):len(fields) + len(afields)] == [getattr(_lib.AttnParams, f).offset for f in afields]
+    assert offs[len(fields) + len(afields):] == [getattr(_lib.GemmChoice, f).offset for f in cfields]
+    assert (_lib.GEMM_REJECTED, _lib.GEMM_GEMV, _lib.GEMM_REG_TILE, _lib.GEMM_LDS_DMA, _lib.GEMM_SEPARATELY) == tuple(
+        int(re.search(r"MMT_GEMM_%s = (\d)" % n, open(HEADER).read()).group(1))
+        for n in ("REJECTED", "GEMV", "REG_TILE", "LDS_DMA", "SEPARATELY"))
+
+
+SELECT_MAIN = r"""
+#include <stdio.h>
+#include <string.h>
+#include "mmt_hip.h"
+static mmt_gemm_params base(int M, int N, int K, int groups) {
+    mmt_gemm_params p;
+    memset(&p, 0, sizeof p);
+    for (int g = 0; g < groups; ++g) {  /* addresses that are never read */
+        p.a[g] = (const void*)0x100000; p.w[g] = (const void*)0x200000; p.c[g] = (void*)0x300000;
+        p.bias[g] = (const float*)0x400000;
+    }
+    p.M = M; p.N = N; p.K = K; p.groups = groups; p.lda = K; p.ldc = N; p.a_seg_rows = M; p.a_segs_a = 1; p.r_p1 = 1;
+    return p;
+}
+static void show(const char* tag, int status, const mmt_gemm_choice* c) {
+    printf("%s %d %d %d %d %d %d %d %d %d\n", tag, status, c->family, c->cfg, c->nsk, c->epi, c->lean, c->form, c->joint,
+           c->wgs);
+}
+int main(void) {
+    mmt_gemm_choice c;
+    mmt_gemm_params p = base(72, 72, 256, 2), q[2];
+    p.c_f32 = 1;
+    show("lean", mmt_gemm_select(&p, 1, MMT_BF16, &c), &c);          /* fp32 C = acc + bias: the lean 64x64 form */
+    p.impl = 10;
+    show("general", mmt_gemm_select(&p, 1, MMT_BF16, &c), &c);
+    p.impl = -1;
+    show("reg", mmt_gemm_select(&p, 1, MMT_F16, &c), &c);
+    p = base(8, 64, 64, 1); p.c_f32 = 1;
+    show("gemv", mmt_gemm_select(&p, 1, MMT_F32, &c), &c);
+    p.M = 0;
+    show("bad", mmt_gemm_select(&p, 1, MMT_F32, &c), &c);
+    q[0] = base(136, 72, 128, 1); q[1] = base(72, 72, 256, 1); q[1].c_f32 = 1;
+    show("multi", mmt_gemm_select(q, 2, MMT_BF16, &c), &c);
+    q[1].ln_fold = 1; q[1].ln_colsum[0] = (const float*)0x500000;
+    show("separately", mmt_gemm_select(q, 2, MMT_BF16, &c), &c);
+    memset(&c, 0, sizeof c);
+    show("null", mmt_gemm_select(NULL, 1, MMT_BF16, &c), &c);
+    return 0;
+}
+"""
+
+
+def test_gemm_select_answers_a_plain_c_program(tmp_path):
+    """mmt_gemm_select from a stand-alone C program linked against the library, on a machine that may have no GPU: it
+    makes no HIP call and never reads through the pointers it is given (here small integers)."""
+    import subprocess
+    from mmt_amd import _lib
+    c = tmp_path / "select.c"
+    c.write_text(SELECT_MAIN)
+    exe = tmp_path / "select"
+    libdir = os.path.dirname(_lib.LIB_PATH)
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.dirname(HEADER), str(c), "-o", str(exe), "-L", libdir,
+                           "-lmmt_hip", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+    got = [ln.split() for ln in subprocess.check_output([str(exe)], env=env).decode().splitlines()]
+    L = _lib
+    #                tag          status family           cfg nsk epi lean form joint wgs
+    assert got == [[str(v) for v in row] for row in (
+        ("lean", 0, L.GEMM_LDS_DMA, 3, 1, 2, 1, 1, 0, 8),
+        ("general", 0, L.GEMM_LDS_DMA, 3, 1, 2, 0, 0, 0, 8),
+        ("reg", 0, L.GEMM_REG_TILE, 0, 0, 0, 0, 0, 0, 8),
+        ("gemv", 0, L.GEMM_GEMV, 0, 0, 0, 0, 0, 0, 16),
+        ("bad", -10000, L.GEMM_REJECTED, 0, 0, 0, 0, 0, 0, 0),
+        ("multi", 0, L.GEMM_LDS_DMA, 3, 1, 0, 0, 0, 2, 10),
+        ("separately", 0, L.GEMM_SEPARATELY, 0, 0, 0, 0, 0, 0, 0),
+        ("null", -10000, L.GEMM_REJECTED, 0, 0, 0, 0, 0, 0, 0))], got
 
 
 def test_bad_arguments_rejected_without_gpu_work():

@@ -30,9 +30,15 @@ def _lib():
     return _lib
 
 
-def _launch(p, dt, name):
+def _launch(p, dt, name, path=None):
+    """Launches p; `path`: fields of mmt_gemm_select's answer for p that must read as given (an LDS-DMA kernel)."""
     L = _lib()
     code = L.MMT_BF16 if dt == torch.bfloat16 else L.MMT_F16
+    if path is not None:
+        c = L.gemm_select(p, code)
+        assert c is not None and c.family == L.GEMM_LDS_DMA, (name, path)
+        got = {k: getattr(c, k) for k in path}
+        assert got == path, (name, got, path)
     L.check(L.LIB.mmt_gemm(p, code, torch.cuda.current_stream().cuda_stream), name)
 
 
@@ -62,7 +68,12 @@ def _fold_case(dname, M, K):
     return _cache[key]
 
 
-def _run_fold(dname, M, K, act, impl, cmap=None):
+# impl 1 / 3 take the lean kernel of the ViT form (FORM 0); impl 10 the general kernel at the same tile, unsplit
+LEAN = {1: dict(lean=1, form=0, cfg=1, bm=128, bn=128, nsk=1), 3: dict(lean=1, form=0, cfg=3, bm=64, bn=64, nsk=1)}
+GENERAL = {k: dict(v, lean=0) for k, v in LEAN.items()}
+
+
+def _run_fold(dname, M, K, act, impl, cmap=None, path=None):
     (x, Wp, colsum, bp, stats), _ = _fold_case(dname, M, K)
     L = _lib()
     rows = M if cmap is None else (M // cmap[0]) * cmap[1]
@@ -75,7 +86,7 @@ def _run_fold(dname, M, K, act, impl, cmap=None):
     p.M, p.N, p.K, p.act, p.groups, p.impl, p.ln_fold, p.ln_eps = M, N, K, act, G, impl, 2, 1e-6
     if cmap is not None:
         p.c_seg_rows, p.c_seg_pitch = cmap
-    _launch(p, DT[dname], "fold")
+    _launch(p, DT[dname], "fold", path)
     torch.cuda.synchronize()
     return out
 
@@ -94,7 +105,7 @@ def _res_case(dname, M, K):
     return _cache[key]
 
 
-def _run_res(dname, M, K, impl, sk=None):
+def _run_res(dname, M, K, impl, sk=None, path=None):
     (x, W, b, R), _ = _res_case(dname, M, K)
     L = _lib()
     c1 = torch.full((G, M, N), float("nan"), device="cuda")
@@ -109,7 +120,7 @@ def _run_res(dname, M, K, impl, sk=None):
     if sk is not None:
         n, ws, cnt = sk
         p.splitk, p.sk_ws, p.sk_ws_floats, p.sk_cnt, p.sk_cnt_n = n, ws.data_ptr(), ws.numel(), cnt.data_ptr(), cnt.numel()
-    _launch(p, DT[dname], "res")
+    _launch(p, DT[dname], "res", path)
     torch.cuda.synchronize()
     return c1, c2, st
 
@@ -133,8 +144,8 @@ def _check_res(dname, M, K, outs, tag):
 @pytest.mark.parametrize("M", [136, 72])
 def test_fold_kernel_bitwise_and_reference(dname, act, K, M):
     """qkv / fc1 form on the 128x128 tile: lean (impl 1) == general (impl 10) bit for bit; both near fp32."""
-    lean = _run_fold(dname, M, K, act, 1)
-    gen = _run_fold(dname, M, K, act, 10)
+    lean = _run_fold(dname, M, K, act, 1, path=LEAN[1])
+    gen = _run_fold(dname, M, K, act, 10, path=GENERAL[1])
     assert torch.equal(_bits(lean), _bits(gen))
     ref = _fold_case(dname, M, K)[1][act]
     err, lim = (lean.float().cpu() - ref).abs().max().item(), 1e-2 * ref.abs().max().item()
@@ -147,8 +158,8 @@ def test_fold_kernel_bitwise_and_reference(dname, act, K, M):
 @pytest.mark.parametrize("M", [72, 136])
 def test_residual_kernel_bitwise_and_reference(dname, K, M):
     """proj / fc2 form on the 64x64 two-k-group tile: C, C2 and the statistics, lean (impl 3) == general (impl 10)."""
-    lean = _run_res(dname, M, K, 3)
-    gen = _run_res(dname, M, K, 10)
+    lean = _run_res(dname, M, K, 3, path=LEAN[3])
+    gen = _run_res(dname, M, K, 10, path=GENERAL[3])
     for a, b in zip(lean, gen):
         assert torch.equal(_bits(a), _bits(b))
     _check_res(dname, M, K, lean, "residual %s M %d K %d" % (dname, M, K))
@@ -157,7 +168,7 @@ def test_residual_kernel_bitwise_and_reference(dname, K, M):
 def test_auto_choice_matches_general_kernel():
     """impl 0 (the frame plan's setting) against impl 10 on parameter sets whose auto tile is the lean kernel's."""
     M, K = 72, 256  # the cost model takes 64x64 for so few tiles
-    for a, b in zip(_run_res("bf16", M, K, 0), _run_res("bf16", M, K, 10)):
+    for a, b in zip(_run_res("bf16", M, K, 0, path=LEAN[3]), _run_res("bf16", M, K, 10, path=GENERAL[3])):
         assert torch.equal(_bits(a), _bits(b))
 
 
@@ -174,7 +185,8 @@ def test_fallback_row_map():
     """An output row map (the template K/V cache passes' qkv) is not a lean parameter set: the general kernel runs
     under impl 0 as under impl 10 (a lean kernel would ignore the map), and the rows land where the map puts them."""
     M, K, seg, pitch = 136, 192, 68, 80
-    a, b = _run_fold("bf16", M, K, 0, 0, cmap=(seg, pitch)), _run_fold("bf16", M, K, 0, 10, cmap=(seg, pitch))
+    a = _run_fold("bf16", M, K, 0, 0, cmap=(seg, pitch), path=dict(lean=0))
+    b = _run_fold("bf16", M, K, 0, 10, cmap=(seg, pitch), path=dict(lean=0))
     assert torch.equal(_bits(a), _bits(b))
     ref = _fold_case("bf16", M, K)[1][0]
     got = a.float().cpu().reshape(G, M // seg, pitch, N)
@@ -183,7 +195,7 @@ def test_fallback_row_map():
     assert (got - ref).abs().max().item() <= 1e-2 * ref.abs().max().item()
     # on the lean kernel's tile shape (impl 1: the map keeps it on the general kernel) the mapped rows hold the bits of
     # the plain launch (impl 10: the general kernel at 128x128 too)
-    got1 = _run_fold("bf16", M, K, 0, 1, cmap=(seg, pitch)).float().cpu().reshape(G, M // seg, pitch, N)
+    got1 = _run_fold("bf16", M, K, 0, 1, cmap=(seg, pitch), path=dict(lean=0, cfg=1)).float().cpu().reshape(G, M // seg, pitch, N)
     assert torch.isnan(got1[:, :, seg:]).all()
     assert torch.equal(got1[:, :, :seg].reshape(G, M, N), _run_fold("bf16", M, K, 0, 10).float().cpu())
 
@@ -193,7 +205,8 @@ def test_fallback_split_k():
     M, K = 136, 320
     ws = torch.empty(1 << 20, device="cuda")
     cnt = torch.zeros(1 << 12, device="cuda", dtype=torch.int32)
-    a, b = _run_res("bf16", M, K, 0, sk=(2, ws, cnt)), _run_res("bf16", M, K, 10, sk=(2, ws, cnt))
+    a = _run_res("bf16", M, K, 0, sk=(2, ws, cnt), path=dict(lean=0, nsk=2))
+    b = _run_res("bf16", M, K, 10, sk=(2, ws, cnt), path=dict(lean=0, nsk=2))
     for u, v in zip(a, b):
         assert torch.equal(_bits(u), _bits(v))
     _check_res("bf16", M, K, a, "split-K")
@@ -203,7 +216,7 @@ def test_fallback_split_k():
 def test_fallback_k_tail():
     """K = 2 x 64 + 24 (three 8-element chunks past the last full step): the general kernel's zero-filled tail."""
     M, K = 136, 152
-    a, b = _run_res("bf16", M, K, 0), _run_res("bf16", M, K, 10)
+    a, b = _run_res("bf16", M, K, 0, path=dict(lean=0)), _run_res("bf16", M, K, 10, path=dict(lean=0))
     for u, v in zip(a, b):
         assert torch.equal(_bits(u), _bits(v))
     _check_res("bf16", M, K, a, "K tail")
@@ -228,7 +241,7 @@ def test_fallback_conv():
         p.lda, p.ldc = cin, cout
         p.M, p.N, p.K, p.act, p.groups, p.impl = B * h * h, cout, 9 * cin, 2, 1, impl
         p.conv_h, p.conv_up, p.conv_cin, p.conv_k3 = h, 1, cin, 1
-        _launch(p, torch.bfloat16, "conv")
+        _launch(p, torch.bfloat16, "conv", dict(lean=0, conv=1))
         torch.cuda.synchronize()
         outs.append(out)
     assert torch.equal(_bits(outs[0]), _bits(outs[1]))

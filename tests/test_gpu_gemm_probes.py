@@ -13,7 +13,6 @@ import pytest
 import torch
 
 import gemm_probes as P
-from test_gpu_ops import _gemm_params, _mn_major
 
 pytestmark = pytest.mark.gpu
 
@@ -23,9 +22,7 @@ def _lib():
     return _lib
 
 
-def _code(dname):
-    L = _lib()
-    return {"f32": L.MMT_F32, "bf16": L.MMT_BF16, "fp16": L.MMT_F16}[dname]
+_code = P.dtype_code
 
 
 _WS = {}
@@ -42,43 +39,18 @@ def _workspace(s):
 
 def _prepare(prob):
     """Uploads a problem's storage and fills mmt_gemm_params; returns (params, device tensors to keep and check)."""
-    s, geo = prob.spec, prob.geo
+    s = prob.spec
     dev = {k: [t.cuda() for t in v] for k, v in prob.inp.items() if isinstance(v, list)}
     out = {k: [t.cuda() for t in v] for k, v in prob.out.items()}
-    ptr = lambda ts: [t.data_ptr() for t in ts]
-    kw = dict(impl=s.impl, act=s.act, c_f32=s.c_f32, c2_copy=s.c2_copy, seg=geo["seg"], k_split=s.k_split,
-              r_mode=s.r_mode, r_p0=s.r_p0, r_p1=s.r_p1, r_t=int(s.r == 2), ldr=geo["ldr"])
-    if s.bias:
-        kw["bias"] = ptr(dev["bias"])
-    if s.r:
-        kw["r"] = ptr(out["c"] if s.r_inplace else dev["r"])
-    if s.c2:
-        kw["c2"] = ptr(out["c2"])
-    if s.k_split:
-        kw["a1"] = ptr(dev["a1"])
-    if s.conv:
-        kw["conv"] = s.conv[:4]
     if s.splitk:
         dev["sk"] = _workspace(s)
-        kw["sk"] = (s.splitk,) + dev["sk"]
-    p = _gemm_params(ptr(dev["a"]), ptr(dev["w"]), ptr(out["c"]), s.M, s.N, s.K, geo["lda"], geo["ldc"], **kw)
-    if s.c_seg:
-        p.c_seg_rows, p.c_seg_pitch = s.c_seg
-    if s.a_t or s.w_t:
-        _mn_major(p, s.a_t, s.w_t, geo["ldw"])
     if s.row_scale_div:
-        dev["row_scale"] = prob.inp["row_scale"].cuda()
-        p.row_scale, p.row_scale_div = dev["row_scale"].data_ptr(), s.row_scale_div
-    for g in range(s.groups):
-        if s.stats:
-            p.ln_stats_out[g] = out["stats"][g].data_ptr()
-        if s.ln_fold:
-            p.ln_colsum[g] = dev["colsum"][g].data_ptr()
-            if s.ln_fold == 2:
-                p.ln_stats_in[g] = dev["stats_in"][g].data_ptr()
-    if s.ln_fold:
-        p.ln_fold, p.ln_eps = s.ln_fold, P.LN_EPS
-    return p, dev, out
+        dev["row_scale"] = [prob.inp["row_scale"].cuda()]
+    held = dict(dev, **out)
+    if s.r_inplace:
+        held["r"] = out["c"]
+    ptrs = {k: [t.data_ptr() for t in v] for k, v in held.items()}
+    return P.params_of(s, ptrs), dev, out
 
 
 def _verify(prob, out, errors, tag=""):

@@ -96,14 +96,30 @@ def _params(dname, G, M, K, impl, out, *, f32, act=0, bias=True, r=False, r_mode
     return p
 
 
+TILE = {1: (128, 128), 2: (128, 64), 3: (64, 64)}
+PL, LR, A2 = 1, 2, 4  # the lean FORM bits: plain, R added, A from two pointers
+
+
+def _path(p, dname, want, n=1):
+    """What mmt_gemm_select says the launch of p (n > 1: of the array p through mmt_gemm_multi) runs: the fields of
+    `want` must read as given (an LDS-DMA kernel in every case of this file)."""
+    L = _lib()
+    c = L.gemm_select(p, _code(DT[dname]), n)
+    assert c is not None and c.family == L.GEMM_LDS_DMA, want
+    got = {k: getattr(c, k) for k in want}
+    assert got == want, (got, want)
+
+
 def _out(dname, G, rows, f32):
     return torch.full((G, rows + PAD, N + PAD), float("nan"), device="cuda", dtype=torch.float32 if f32 else DT[dname])
 
 
-def _run(dname, G, M, K, impl, *, f32, rows=None, **kw):
+def _run(dname, G, M, K, impl, *, f32, rows=None, path=None, **kw):
     L = _lib()
     out = _out(dname, G, M if rows is None else rows, f32)
     p = _params(dname, G, M, K, impl, out, f32=f32, **kw)
+    if path is not None:
+        _path(p, dname, path)
     L.check(L.LIB.mmt_gemm(p, _code(DT[dname]), torch.cuda.current_stream().cuda_stream), "tail gemm")
     torch.cuda.synchronize()
     return out
@@ -122,9 +138,12 @@ def _check(out, ref, f32, tag, rows=None):
 
 
 def _pair(dname, G, M, K, impl, *, f32, **kw):
-    """The lean path (forced tile shape) and impl 10: same bits, sentinels, reference."""
-    lean = _run(dname, G, M, K, impl, f32=f32, **kw)
-    gen = _run(dname, G, M, K, 10, f32=f32, **kw)
+    """The lean path (forced tile shape) and impl 10: same bits, sentinels, reference.  The selection says that the
+    first is the lean kernel of the expected form and the second the general kernel at the same tile, unsplit."""
+    form = PL | (LR if kw.get("r") else 0) | (A2 if kw.get("k_split") else 0)
+    tile = dict(cfg=impl, bm=TILE[impl][0], bn=TILE[impl][1], nsk=1)
+    lean = _run(dname, G, M, K, impl, f32=f32, path=dict(tile, lean=1, form=form), **kw)
+    gen = _run(dname, G, M, K, 10, f32=f32, path=dict(tile, lean=0, form=0), **kw)
     assert torch.equal(_bits(lean), _bits(gen))
     rk = {k: kw[k] for k in ("act", "bias", "r", "k_split") if k in kw}
     if kw.get("r_mode") == 1:
@@ -172,7 +191,8 @@ def test_c16_relu_form_bitwise_and_reference(dname, K, G):
 def test_auto_choice_matches_general_kernel():
     """impl 0 (the frame plan's setting) on shapes whose auto tile is the lean kernel's (64x64 for so few tiles)."""
     for kw in (dict(f32=True, r=True), dict(f32=True, k_split=128), dict(f32=False)):
-        a, b = _run("bf16", 2, 72, 256, 0, **kw), _run("bf16", 2, 72, 256, 10, **kw)
+        a = _run("bf16", 2, 72, 256, 0, path=dict(lean=1, cfg=3), **kw)
+        b = _run("bf16", 2, 72, 256, 10, path=dict(lean=0, cfg=3, nsk=1), **kw)
         assert torch.equal(_bits(a), _bits(b))
 
 
@@ -186,7 +206,7 @@ def test_edge_identity_row_map_inside(r_p0):
 
 def test_edge_row_map_wraps_outside():
     """r_p0 = M / 2: rows wrap, the general kernel runs and matches a reference that wraps."""
-    out = _run("bf16", 2, 72, 192, 3, f32=True, r=True, r_mode=1, r_p0=36)
+    out = _run("bf16", 2, 72, 192, 3, f32=True, r=True, r_mode=1, r_p0=36, path=dict(lean=0, cfg=3, epi=0))
     _check(out, _ref("bf16", 2, 72, 192, f32=True, r=True, r_p0=36), True, "r_p0 36")
     assert not torch.equal(_bits(out), _bits(_run("bf16", 2, 72, 192, 3, f32=True, r=True)))
 
@@ -194,16 +214,16 @@ def test_edge_row_map_wraps_outside():
 def test_edge_k_split():
     """k_split = 64 is a lean parameter set, 72 (inside a K-step) is not; both meet their references."""
     _pair("bf16", 2, 72, 192, 3, f32=True, k_split=64)
-    out = _run("bf16", 2, 72, 192, 3, f32=True, k_split=72)
+    out = _run("bf16", 2, 72, 192, 3, f32=True, k_split=72, path=dict(lean=0, cfg=3))
     _check(out, _ref("bf16", 2, 72, 192, f32=True, k_split=72), True, "k_split 72")
 
 
 def test_edge_bias():
     """With the bias lean, without it the general kernel."""
     _pair("bf16", 2, 72, 192, 3, f32=True, bias=True)
-    out = _run("bf16", 2, 72, 192, 3, f32=True, bias=False)
+    out = _run("bf16", 2, 72, 192, 3, f32=True, bias=False, path=dict(lean=0, cfg=3))
     _check(out, _ref("bf16", 2, 72, 192, f32=True, bias=False), True, "no bias")
-    out = _run("bf16", 2, 72, 192, 3, f32=False, bias=False)
+    out = _run("bf16", 2, 72, 192, 3, f32=False, bias=False, path=dict(lean=0, cfg=3))
     _check(out, _ref("bf16", 2, 72, 192, f32=False, bias=False), False, "no bias, 16-bit C")
 
 
@@ -212,7 +232,7 @@ def test_edge_output_row_map():
     40, the rows between and after them untouched."""
     _pair("bf16", 2, 72, 192, 3, f32=True)
     seg, pitch = 36, 40
-    out = _run("bf16", 2, 72, 192, 3, f32=True, rows=2 * pitch, cmap=(seg, pitch))
+    out = _run("bf16", 2, 72, 192, 3, f32=True, rows=2 * pitch, cmap=(seg, pitch), path=dict(lean=0, cfg=3, epi=0))
     _check(out, None, True, "row map", rows=2 * pitch)
     got = out.float().cpu()[:, :2 * pitch, :N].reshape(2, 2, pitch, N)
     assert torch.isnan(got[:, :, seg:]).all()
@@ -226,7 +246,7 @@ def test_edge_forced_split_k():
     _pair("bf16", 2, 72, 320, 3, f32=True, r=True)
     ws = torch.empty(1 << 20, device="cuda")
     cnt = torch.zeros(1 << 12, device="cuda", dtype=torch.int32)
-    out = _run("bf16", 2, 72, 320, 3, f32=True, r=True, sk=(2, ws, cnt))
+    out = _run("bf16", 2, 72, 320, 3, f32=True, r=True, sk=(2, ws, cnt), path=dict(lean=0, cfg=3, nsk=2))
     _check(out, _ref("bf16", 2, 72, 320, f32=True, r=True), True, "split-K")
     assert int(cnt.abs().sum()) == 0
 
@@ -250,6 +270,8 @@ def test_multi_bitwise(dname, bias1):
             L.check(L.LIB.mmt_gemm(p1, _code(DT[dname]), st), "offsets")
         else:
             arr = (L.GemmParams * 2)(p0, p1)
+            # the lean multi kernel (its second problem's form takes the bias or its absence) / the general one
+            _path(arr, dname, dict(joint=2, cfg=3, lean=int(impl == 0), form=(PL | LR | A2 | 8) * (impl == 0)), n=2)
             L.check(L.LIB.mmt_gemm_multi(arr, 2, _code(DT[dname]), st), "multi")
         torch.cuda.synchronize()
         res.append((o0, o1))

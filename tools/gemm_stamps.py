@@ -33,7 +33,6 @@ if os.environ.get("GEMM_STAMP_SHAPES") == "frame":
 if os.environ.get("GEMM_STAMP_SHAPES") == "train":  # the training step's forward GEMMs (16 pairs: 8448 rows per backbone)
     SHAPES = [("t_qkv", 1, 8448, 2304, 768, 0, 0), ("t_fc1", 1, 8448, 3072, 768, 1, 0), ("t_proj", 1, 8448, 768, 768, 0, 1),
               ("t_fc2", 1, 8448, 768, 3072, 0, 1)]
-TILES = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 128), 8: (128, 128)}
 IMPLS = [int(x) for x in os.environ.get("GEMM_STAMP_IMPLS", "1,2,3,4").split(",")]
 SK_WS = None
 
@@ -75,18 +74,10 @@ def main():
             for _ in range(10):
                 L.check(L.LIB.mmt_gemm(ctypes.byref(p), L.MMT_BF16, s), name)
             torch.cuda.synchronize()
-            if impl in (0, 10):  # grid unknown here: the rows the last launch wrote (ended within 30 us of the last end)
-                buf = (ctypes.c_ulonglong * (4096 * 8))()
-                L.check(L.LIB.mmt_gemm_stamps(buf, 4096 * 8), "stamps")
-                st = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.int64)
-                st = st[st[:, 7] >= st[:, 7].max() - 3000]
-                nwg = st.shape[0]
-            else:
-                bm, bn = TILES[impl]
-                nwg = ((M + bm - 1) // bm) * ((N + bn - 1) // bn) * G
-                buf = (ctypes.c_ulonglong * (nwg * 8))()
-                L.check(L.LIB.mmt_gemm_stamps(buf, nwg * 8), "stamps")
-                st = np.frombuffer(buf, dtype=np.uint64).reshape(nwg, 8).astype(np.int64)
+            nwg = L.gemm_select(p, L.MMT_BF16).wgs  # the launch's workgroups, whatever tile and K split it resolved to
+            buf = (ctypes.c_ulonglong * (nwg * 8))()
+            L.check(L.LIB.mmt_gemm_stamps(buf, nwg * 8), "stamps")
+            st = np.frombuffer(buf, dtype=np.uint64).reshape(nwg, 8).astype(np.int64)
             rt0, c0, c1, c2, e1, e2, c3, rt1 = st.T
             freq = np.median((c3 - c0) / np.maximum(rt1 - rt0, 1)) * 100.0  # MHz (realtime = 100 MHz)
             row = {"gemm": name, "impl": impl, "nwg": nwg, "clock_mhz": round(float(freq), 0),
