@@ -87,6 +87,13 @@ extern "C" {
  *   input images a_stride_a pixels apart (0: packed, (conv_h/conv_up)^2).  conv_k3=2: the 3x3 taps
  *   read in reverse order (input pixel (y+1-ky, x+1-kx)), i.e. the convolution with the flipped
  *   kernel -- the data gradient of a 3x3 conv from its unflipped weights [Cin][ky][kx][Cout].
+ *   k_split > 0 (channel split): the input is the channel concatenation of two NHWC maps that is never
+ *   materialised -- within each tap, channels [0, k_split) of a pixel come from a[g] and [k_split, conv_cin)
+ *   from a1[g]; both maps have pixel stride lda and image pitch a_stride_a and hold k_split resp.
+ *   conv_cin - k_split contiguous channels per pixel.  k is numbered as above, so W [cout][3][3][conv_cin] is the
+ *   concatenated tensor's.  Needs k_split % 8 == 0, k_split < conv_cin, conv_up == 1, conv_k3 != 2 and a1[g]
+ *   16-byte aligned (else MMT_EBADARG); the LDS-DMA kernel takes k_split % 64 == 0, the register-staged
+ *   kernel the rest.  k_split == 0: one map, a1 is not read.
  * Epilogue: v = act(acc + bias) with act 0 none / 1 GELU(erf) / 2 ReLU / 5 GELU backward:
  *   v = (acc + bias) * GELU'(R) (R then not added; 16-bit LDS-DMA kernels);
  *   c2 == NULL: C = v (+ R if r != NULL);  c2 != NULL: C = v, C2 = v + R (c2_copy 1: C = v (+ R),

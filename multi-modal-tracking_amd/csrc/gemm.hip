@@ -115,7 +115,9 @@ __global__ __launch_bounds__(256 * KS) void gemm_kernel(const mmt_gemm_params p)
                 v_ = v_ && iy_ >= 0 && ix_ >= 0 && iy_ < ch && ix_ < ch;                                 \
                 iy_ = min(max(iy_, 0), ch - 1);                                                          \
                 ix_ = min(max(ix_, 0), ch - 1);                                                          \
-                src_ = A0 + (aoff[i] + (int64_t)(iy_ / cup) * hi + (ix_ / cup)) * p.lda + ci_;            \
+                const bool hp_ = p.k_split > 0 && ci_ >= p.k_split; /* channel split: the second map */   \
+                src_ = (hp_ ? A1 : A0) + (aoff[i] + (int64_t)(iy_ / cup) * hi + (ix_ / cup)) * p.lda +    \
+                       (hp_ ? ci_ - p.k_split : ci_);                                                    \
             }                                                                                            \
             SA[i] = *(const u32x4*)src_;                                                                 \
             ok_ |= (uint32_t)v_ << i;                                                                    \
@@ -317,6 +319,9 @@ int check_gemm(const mmt_gemm_params& p) {
         if (p.conv_cin % EPC || p.conv_up < 1 || p.conv_h % p.conv_up) return MMT_EBADARG;
         if (p.conv_k3 < 0 || p.conv_k3 > 2 || p.K != (p.conv_k3 ? 9 : 1) * p.conv_cin) return MMT_EBADARG;
         if (p.M % (p.conv_h * p.conv_h)) return MMT_EBADARG;
+        // channel split (input = two NHWC maps): whole 16-B chunks of 16-bit elements on either side, plain taps
+        if (p.k_split < 0 || p.k_split % 8) return MMT_EBADARG;
+        if (p.k_split > 0 && (p.k_split >= p.conv_cin || p.conv_up > 1 || p.conv_k3 == 2)) return MMT_EBADARG;
     } else {
         if (p.a_seg_rows <= 0 || p.a_segs_a <= 0) return MMT_EBADARG;
         if (p.k_split % EPC || p.a_stride_a % EPC || p.a_stride_b % EPC) return MMT_EBADARG;
@@ -335,7 +340,7 @@ int check_gemm(const mmt_gemm_params& p) {
     for (int g = 0; g < p.groups; ++g) {
         if (!p.a[g] || !p.w[g] || !p.c[g]) return MMT_EBADARG;
         if (((uintptr_t)p.a[g] | (uintptr_t)p.w[g]) & 15) return MMT_EBADARG;
-        if (p.k_split > 0 && p.conv_h == 0 && (!p.a1[g] || ((uintptr_t)p.a1[g] & 15))) return MMT_EBADARG;
+        if (p.k_split > 0 && (!p.a1[g] || ((uintptr_t)p.a1[g] & 15))) return MMT_EBADARG;
         if (p.c2[g] && !p.r[g] && p.c2_copy < 2) return MMT_EBADARG;
         if ((p.act == 5 && !p.r[g]) || (p.c2_copy >= 2 && !p.c2[g])) return MMT_EBADARG;
         if (p.c2_copy >= 3 && (p.N % 8 || p.ldc < p.N - 8)) return MMT_EBADARG;

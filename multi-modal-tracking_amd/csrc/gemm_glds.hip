@@ -387,12 +387,15 @@ MMT_DEV void gemm_glds_tile(const P& p, const int g, const int tile, const int s
                 dy = ty - 1;
                 dx = (int)tf - ty * 3 - 1;
             }
+            // channel split: channels [ks, cin) of every pixel come from the second map (same pixel stride and
+            // image pitch); only this lane's source base changes
+            const T* ab = ks > 0 && ci >= ks ? A1 - ks : A0;
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
                 const int iy = ay[i] + dy, ix = ax[i] + dx;
                 const bool ok = kin && iy >= 0 && ix >= 0 && iy < ch && ix < ch;
                 const uint32_t pix = (uint32_t)aoff[i] + (uint32_t)((iy >> cup_sh) * hi + (ix >> cup_sh));
-                const T* src = A0 + (pix * (uint32_t)p.lda + (uint32_t)ci);
+                const T* src = ab + (pix * (uint32_t)p.lda + (uint32_t)ci);
                 glds16(ok ? (const void*)src : (const void*)g_zero_chunk, base + (wid * PA + i) * 1024);
             }
         }
@@ -1428,6 +1431,7 @@ bool glds_takes(const mmt_gemm_params& p) {
         const int64_t imgs = (p.M + (int64_t)p.conv_h * p.conv_h - 1) / ((int64_t)p.conv_h * p.conv_h);
         const int64_t pitch = p.a_stride_a > 0 ? p.a_stride_a : (int64_t)hi * hi;
         if ((imgs * pitch * (int64_t)p.lda + p.K) >= ((int64_t)1 << 32) || p.K >= (1 << 24)) return false;
+        if (p.k_split % 64) return false;  // channel split: on a K-step boundary only (else the register-staged kernel)
     }
     if (p.lda % 8 || p.a_stride_a % 8 || p.a_stride_b % 8 || p.k_split % 8) return false;
     if (p.a_seg_rows > INT32_MAX || p.a_segs_a > INT32_MAX) return false;

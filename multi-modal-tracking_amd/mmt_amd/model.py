@@ -17,8 +17,8 @@ HIP device and libmmt_hip.so the forward raises.
 
 Scope: inference (eval) of the hot path.  The deformable fusion front-ends (FUSION_CLASSES:
 Attention_Fusion_Bimodal, _LNSpecific, _LNSpecific_Sum, _LNSpecific_2, all run as the LNSpecific plan
-with weights tied) and head CORNER_UP only; the reference's other fusion/head
-classes are ablations out of scope.  Deviation D1: the fusion width follows MODEL.HIDDEN_DIM instead of the reference's
+with weights tied), on the shared-backbone builders also the concat-conv RGBT_Fusion_Cat, and head CORNER_UP only
+(SURVEY §2 rows 5, 8); the reference's other fusion/head classes are ablations out of scope.  Deviation D1: the fusion width follows MODEL.HIDDEN_DIM instead of the reference's
 hard-coded 768, so ViT-L (HIDDEN_DIM 1024) builds; for ViT-B both are 768.
 """
 import math
@@ -197,10 +197,34 @@ class Attention_Fusion_Bimodal_LNSpecific_2(nn.Module):
         self.adjust_out = _adjust(d_model, channels_num)
 
 
+class RGBT_Fusion_Cat(nn.Module):
+    """fusion_utils.py:86-110 parameters: three Conv3x3(bias=False) -> BatchNorm2d -> ReLU stages on
+    cat([search_v, search_i], 1): 2C -> 2C -> C -> C.  Only the channel count is used; the builders' other
+    arguments are accepted and dropped, as in the reference."""
+
+    def __init__(self, channels_num, *args, **kwargs):
+        super().__init__()
+        c = channels_num
+        self.fusion1 = nn.Conv2d(2 * c, 2 * c, 3, 1, 1, bias=False)
+        self.fusion1_bn = nn.BatchNorm2d(2 * c)
+        self.fusion1_relu = nn.ReLU(inplace=True)
+        self.fusion2 = nn.Conv2d(2 * c, c, 3, 1, 1, bias=False)
+        self.fusion2_bn = nn.BatchNorm2d(c)
+        self.fusion2_relu = nn.ReLU(inplace=True)
+        self.fusion3 = nn.Conv2d(c, c, 3, 1, 1, bias=False)
+        self.fusion3_bn = nn.BatchNorm2d(c)
+        self.fusion3_relu = nn.ReLU(inplace=True)
+
+
 # MODEL.FUSION_CLASS values the builders accept: the deformable front-ends, each of which is the LNSpecific
 # one with some weights tied (fusion_parts below; DESIGN.md §4)
 FUSION_CLASSES = {c.__name__: c for c in (Attention_Fusion_Bimodal, Attention_Fusion_Bimodal_LNSpecific,
                                           Attention_Fusion_Bimodal_LNSpecific_Sum, Attention_Fusion_Bimodal_LNSpecific_2)}
+# ... and the concat-conv front-end, which the stacked builders (one backbone over both modalities) take: the
+# reference ships it with the asymmetric shared yaml only, so the two-stream builder keeps refusing it
+STACKED_FUSION_CLASSES = dict(FUSION_CLASSES, RGBT_Fusion_Cat=RGBT_Fusion_Cat)
+CAT_BUILDERS = ("build_mixformer_vit_rgbt_shared", "build_mixformer_vit_rgbt_uni", "build_asymmetric_shared",
+                "build_asymmetric_shared_online_score", "build_asymmetric_shared_ce")
 
 
 def fusion_parts(fu):
@@ -613,10 +637,16 @@ def _vit_spec(cfg):
     raise KeyError("VIT_TYPE shoule set to 'large_patch16' or 'base_patch16'")
 
 
-def _check_cfg(cfg):
-    if cfg.MODEL.FUSION_CLASS not in FUSION_CLASSES:
-        raise NotImplementedError("FUSION_CLASS %r: only the deformable front-ends %s are implemented on MI355X"
-                                  % (cfg.MODEL.FUSION_CLASS, ", ".join(sorted(FUSION_CLASSES))))
+def _check_cfg(cfg, stacked=True):
+    """stacked: one backbone over both modalities (every builder but the two-stream one)."""
+    name = cfg.MODEL.FUSION_CLASS
+    if name == "RGBT_Fusion_Cat" and not stacked:
+        raise NotImplementedError("FUSION_CLASS 'RGBT_Fusion_Cat' is built by the shared-backbone builders (%s), not by "
+                                  "the two-stream build_mixformer_vit_rgbt: the reference ships it with the asymmetric "
+                                  "shared model only" % ", ".join(CAT_BUILDERS))
+    if name not in STACKED_FUSION_CLASSES:
+        raise NotImplementedError("FUSION_CLASS %r: only the deformable front-ends %s and RGBT_Fusion_Cat (shared-backbone "
+                                  "builders) are implemented on MI355X" % (name, ", ".join(sorted(FUSION_CLASSES))))
     if cfg.MODEL.HEAD_TYPE != "CORNER_UP":
         raise NotImplementedError("HEAD_TYPE %r: only CORNER_UP is implemented on MI355X" % cfg.MODEL.HEAD_TYPE)
 
@@ -634,7 +664,7 @@ def _head(cfg):
 
 
 def _fusion(cfg):
-    return FUSION_CLASSES[cfg.MODEL.FUSION_CLASS](cfg.MODEL.HIDDEN_DIM, 512, 2, cfg.MODEL.FUSION_LAYERS)
+    return STACKED_FUSION_CLASSES[cfg.MODEL.FUSION_CLASS](cfg.MODEL.HIDDEN_DIM, 512, 2, cfg.MODEL.FUSION_LAYERS)
 
 
 def _load_checkpoint(path, key):
@@ -682,7 +712,7 @@ def _load_rgb_tracker(model, path, two_stream):
 
 
 def build_mixformer_vit_rgbt(cfg, train=True):
-    _check_cfg(cfg)
+    _check_cfg(cfg, stacked=False)
     bv, bi = _backbone(cfg, False), _backbone(cfg, False)
     if train:
         _load_mae(bv, cfg, False)

@@ -57,7 +57,10 @@ class Dims:
         self.ntok = self.n_t + self.ns
         self.hidden = sd[pre + "blocks.0.mlp.fc1.weight"].shape[0]
         self.nmod = 1 if variant == "rgb" else 2  # modalities (sequences per frame)
-        fusion = self.nmod == 2  # the RGB-only model has no fusion: the head reads the backbone
+        # RGBT_Fusion_Cat (fusion_utils.py:86-110): three 3x3 conv + BatchNorm + ReLU stages on the channel
+        # concatenation of the two search maps; no adjust convs, no deformable encoder
+        self.cat = self.nmod == 2 and "fusion_vi.fusion1.weight" in sd
+        fusion = self.nmod == 2 and not self.cat  # the RGB-only model has no fusion: the head reads the backbone
         adj = "fusion_vi.adjust_in.0.weight" if "fusion_vi.adjust_in.0.weight" in sd else "fusion_vi.adjust_v.0.weight"
         self.d_model = sd[adj].shape[0] if fusion else 512
         self.fusion_layers = 0
@@ -140,12 +143,13 @@ class MixFormerRGBTRuntime:
     def _TH(self, x):  # head storage type
         return x.detach().to(self.device, self.hdtype).contiguous()
 
-    def _fold(self, sd, name):
-        """conv() block (head.py:7-20): Conv3x3 -> BatchNorm2d(eval) -> ReLU, BN folded."""
-        w = sd[name + ".0.weight"].double()
-        b = sd[name + ".0.bias"].double()
-        g, beta = sd[name + ".1.weight"].double(), sd[name + ".1.bias"].double()
-        mean, var = sd[name + ".1.running_mean"].double(), sd[name + ".1.running_var"].double()
+    def _fold(self, sd, name, conv=".0", bn=".1"):
+        """conv() block (head.py:7-20): Conv3x3 -> BatchNorm2d(eval) -> ReLU, BN folded.  conv / bn: the key
+        suffixes of the two modules (RGBT_Fusion_Cat: name, name + "_bn"; its convs have no bias)."""
+        w = sd[name + conv + ".weight"].double()
+        b = sd[name + conv + ".bias"].double() if name + conv + ".bias" in sd else w.new_zeros(w.shape[0])
+        g, beta = sd[name + bn + ".weight"].double(), sd[name + bn + ".bias"].double()
+        mean, var = sd[name + bn + ".running_mean"].double(), sd[name + bn + ".running_var"].double()
         s = g / torch.sqrt(var + 1e-5)
         w = w * s.view(-1, 1, 1, 1)
         b = (b - mean) * s + beta
@@ -214,6 +218,18 @@ class MixFormerRGBTRuntime:
         d, W = self.d, self.w
         C = d.C
         f = "fusion_vi."
+        if d.cat:
+            # RGBT_Fusion_Cat: conv3x3(2C -> 2C) -> conv3x3(2C -> C) -> conv3x3(C -> C), each + BatchNorm(eval,
+            # folded) + ReLU, in the head convs' operand layout [cout][(ky, kx, cin)].  The first two run in the
+            # compute dtype (the first reads the backbone output in place), the third feeds the head.
+            for i, (cin, cout) in enumerate(((2 * C, 2 * C), (2 * C, C), (C, C)), 1):
+                shape = tuple(sd[f + "fusion%d.weight" % i].shape)
+                if shape != (cout, cin, 3, 3):
+                    raise ValueError("fusion_vi.fusion%d.weight: shape %s, expected %s" % (i, shape, (cout, cin, 3, 3)))
+                w_, b_ = self._fold(sd, f + "fusion%d" % i, conv="", bn="_bn")
+                W["cat%d.w" % i], W["cat%d.b" % i] = self._T(w_), self._F(b_)
+            W["cat.zero"] = torch.zeros(C, device=self.device, dtype=torch.float32)
+            return
         # The front-end is read from the keys present.  Each of the reference's deformable front-ends is
         # Attention_Fusion_Bimodal_LNSpecific with some weights tied (fusion_utils.py:165-353), so all of them
         # fill the same W[...] entries and run the same launch list; a tied pair is one device tensor:
@@ -359,6 +375,10 @@ class MixFormerRGBTRuntime:
             "BOX": e(B, 4, t=f32), "XYXY": e(B, 4, t=f32), "ROIS": e(B, 5, t=f32),
             "MAPS": e(2, B, d.fh * d.fh, t=f32),
         }
+        if d.cat:  # RGBT_Fusion_Cat: the two intermediate maps instead of the encoder's streams
+            for k in ("Y1", "SRC", "SRCT", "VAL", "OFFW", "MS", "SRC2", "H2", "Y2"):
+                ws[k] = None
+            ws.update({"CAT1": e(B * ns, 2 * C), "CAT2": e(B * ns, C)})
         if self.variant == "asym_online":
             ws.update({"ROIT": e(B * 16, C, t=f32), "KV0": e(B * 16, 2 * C, t=f32), "AT": e(B, C, t=f32),
                        "XS": e(B, C, t=f32), "Q1": e(B, C, t=f32), "KV1": e(B * d.n_t, 2 * C, t=f32),
@@ -672,9 +692,37 @@ class MixFormerRGBTRuntime:
                              None))
             self._plan_head(plan, ws, score, P(XT, t0 * C), C, None if compact else (max(B * ns, 1), 1, ntok, 0))
             return plan
+        Mf = B * ns
+        if d.cat:
+            # --- RGBT_Fusion_Cat: three 3x3 conv + folded BatchNorm + ReLU launches.  The first reads the channel
+            # concatenation of the two modalities' search rows in place through the conv mode's channel split (a / a1,
+            # k_split = C; one gs x gs NHWC image every ntok rows of the backbone output, every ns in the compact pass).
+            gs = d.gs
+            self._gemm(plan, "fusion_cat1", a=[P(XT, t0 * C)], a1=[P(XT, B * ntok * C + t0 * C)], k_split=C,
+                       w=[P(W["cat1.w"])], c=[P(ws["CAT1"])], M=Mf, N=2 * C, K=9 * 2 * C, lda=C, ldc=2 * C,
+                       bias=[P(W["cat1.b"])], act=2, conv=(gs, 1, 2 * C, 1), seg=(max(Mf, 1), 1, ntok, 0))
+            self._gemm(plan, "fusion_cat2", a=[P(ws["CAT1"])], w=[P(W["cat2.w"])], c=[P(ws["CAT2"])], M=Mf, N=C,
+                       K=9 * 2 * C, lda=2 * C, ldc=C, bias=[P(W["cat2.b"])], act=2, conv=(gs, 1, 2 * C, 1))
+            # the third writes the fused map in fp32 (FUS, the score head's RoI pool) and in the head's storage type
+            # (FUST): for a 16-bit head of the compute dtype as the GEMM's 16-bit copy C2 (its residual operand is
+            # one row of zeros), else through a cast launch; an fp32 head reads FUS itself
+            k3 = dict(a=[P(ws["CAT2"])], w=[P(W["cat3.w"])], c=[P(ws["FUS"])], M=Mf, N=C, K=9 * C, lda=C, ldc=C,
+                      bias=[P(W["cat3.b"])], act=2, conv=(gs, 1, C, 1), c_f32=1)
+            fused = ws["FUST"]
+            if self.hdtype == torch.float32:
+                self._gemm(plan, "fusion_cat3", **k3)
+                fused = ws["FUS"]
+            elif self.hdtype == self.dtype:
+                self._gemm(plan, "fusion_cat3", c2=[P(ws["FUST"])], c2_copy=1, r=[P(W["cat.zero"])], ldr=C, r_mode=1,
+                           r_p0=1, **k3)
+            else:
+                self._gemm(plan, "fusion_cat3", **k3)
+                plan.append((LIB.mmt_add_cast, (P(ws["FUS"]), None, 0, None, P(ws["FUST"]), Mf * C, self.hcdt),
+                             "fusion_cat_cast", None))
+            self._plan_head(plan, ws, score, P(fused), C, None, spm_kv1)
+            return plan
         # --- fusion: adjust_v / adjust_i (1x1 conv on the search tokens) + GroupNorm
         Y1, SRC, SRCT, VAL = ws["Y1"], ws["SRC"], ws["SRCT"], ws["VAL"]
-        Mf = B * ns
         self._gemm(plan, "fusion_adjust", a=[P(XT, t0 * C), P(XT, B * ntok * C + t0 * C)],
                    w=[P(W["adj_v.w"]), P(W["adj_i.w"])], c=[P(Y1), P(Y1, Mf * dm)], M=Mf, N=dm, K=C, lda=C, ldc=dm,
                    bias=[P(W["adj_v.b"]), P(W["adj_i.b"])], seg=None if compact else (ns, 1 << 30, ntok * C, 0), c_f32=1)

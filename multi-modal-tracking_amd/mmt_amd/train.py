@@ -879,7 +879,8 @@ class _HipConv3x3(torch.autograd.Function):
         check(LIB.mmt_im2col3x3_cm_bf16(x.data_ptr(), col.data_ptr(), B, Ho, Ho, Cin, up, _stream()),
               "mmt_im2col3x3_cm_bf16")
         dw, db = _weight_grads(dy.view(M, Cp), col, M, Cp, 9 * Cin)
-        return dx, dw[:Cout].view(ctx.wshape), db[:Cout], None, None, None
+        # (a conv without bias, RGBT_Fusion_Cat's: no gradient for the None input)
+        return dx, dw[:Cout].view(ctx.wshape), db[:Cout] if ctx.needs_input_grad[2] else None, None, None, None
 
 
 class _HipMSDABimodal(torch.autograd.Function):
@@ -1889,13 +1890,54 @@ def _ref_points(H, W, B, L, device):
     return ref[:, :, None].expand(B, ref.shape[1], L, 2)
 
 
+def _cat_fusion_forward(fu, s_v, s_i, ops):
+    """RGBT_Fusion_Cat.forward (fusion_utils.py:105-110): three Conv3x3 -> BatchNorm2d -> ReLU stages on the channel
+    concat of the two search maps -> (B, C, h, w).  On HipOps: NHWC bf16 maps, the convolutions on ops.conv3x3
+    (forward, dX and dW on the HIP GEMM as the corner head's), each norm + ReLU on ops.bn_relu with the module's
+    train / eval semantics (a training SyncBatchNorm's statistics over its process group).  The concat is made once
+    (one aten cat forward; its backward hands the two halves of fusion1's dX [B h w][2C] back as views): token
+    rows (2B, ns, C) from the backbones (s_i None) or two NCHW maps."""
+    conv3x3, bn_relu = getattr(ops, "conv3x3", None), getattr(ops, "bn_relu", None)
+    if s_i is None:  # both modalities' search tokens as bf16 rows (2B, ns, C)
+        b, P, C = s_v.shape[0] // 2, s_v.shape[1], s_v.shape[2]
+        h = w = int(round(P ** 0.5))
+        if h * w != P or conv3x3 is None:
+            raise ValueError("fusion_forward: token-row inputs need the HIP convolutions (HipOps), square maps")
+        x = torch.cat([s_v[:b], s_v[b:]], 2).view(b, h, w, 2 * C)
+    elif conv3x3 is not None:
+        x = torch.cat([s_v.permute(0, 2, 3, 1), s_i.permute(0, 2, 3, 1)], 3)  # NHWC straight from the cat
+    else:  # the modules as the reference runs them (CPU stand-ins of the ops)
+        x = torch.cat([s_v, s_i], 1)
+        for i in (1, 2, 3):
+            x = getattr(fu, "fusion%d_relu" % i)(getattr(fu, "fusion%d_bn" % i)(getattr(fu, "fusion%d" % i)(x)))
+        return x
+    global _BN_TRACKED
+    outer, _BN_TRACKED = _BN_TRACKED, ([] if bn_relu is not None else None)
+    try:
+        for i in (1, 2, 3):
+            cv, bn = getattr(fu, "fusion%d" % i), getattr(fu, "fusion%d_bn" % i)
+            y = conv3x3(x.contiguous(), cv.weight, cv.bias)
+            if bn_relu is not None and _hip_bn_ok(bn):
+                x = bn_relu(y, bn)
+            else:  # cumulative-average norms and SYNC_BN_COLLECTIVE "off": the module on the NCHW map (as the head)
+                x = F.relu(bn(y.permute(0, 3, 1, 2).contiguous())).permute(0, 2, 3, 1).contiguous()
+        if _BN_TRACKED:
+            torch._foreach_add_(_BN_TRACKED, 1)
+    finally:
+        _BN_TRACKED = outer
+    return x.permute(0, 3, 1, 2)
+
+
 def fusion_forward(fu, s_v, s_i, ops):
     """Attention_Fusion_Bimodal_LNSpecific.forward (fusion_utils.py:270-279) with the deformable
     encoder (deformable_encoder_lnspecific.py:131-160) and MSDeformAttn_Bimodal
     (ms_deform_attn_bimodal.py:83-130).  The other deformable front-ends (Attention_Fusion_Bimodal,
     _LNSpecific_Sum, _LNSpecific_2; fusion_utils.py:165-353) are this one with weights tied: model.fusion_parts /
     layer_norms hand the same module for both modalities and the grouped ops get its Parameters twice, so autograd
-    sums the two gradients into them; the summed tail runs as [W | W] on the concat (_adjust_tokens)."""
+    sums the two gradients into them; the summed tail runs as [W | W] on the concat (_adjust_tokens).
+    RGBT_Fusion_Cat (fusion_utils.py:86-110) has its own route, _cat_fusion_forward."""
+    if hasattr(fu, "fusion1"):
+        return _cat_fusion_forward(fu, s_v, s_i, ops)
     adj_v, adj_i, tail, summed = fusion_parts(fu)
     tokens = getattr(ops, "group_norm", None) is not None  # adjust_* on token rows (HIP GEMM + GroupNorm)
     if s_i is None:  # both modalities' search tokens as bf16 rows (2B, ns, C) (_backbones_rgbt tokens=True)
