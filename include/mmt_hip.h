@@ -53,6 +53,8 @@
  *       :124-131, lib/utils/box_ops.py:155-164
  *   mmt_sample_target_table / mmt_track_update_slots  the same two for N sequences per launch (the
  *       batched tracker): crop descriptors in a device table, per-slot frame size and active mask
+ *   mmt_sample_target_packed / mmt_track_update_packed  the same two indexed by a slot list in device
+ *       memory (the batched tracker's packed step: the model runs at a smaller batch on the active slots only)
  *   mmt_slot_copy               no reference counterpart: moves the rows of listed tracker slots between a
  *       compact staging layout and the N-slot layout (the batched tracker's per-slot template K/V cache:
  *       template crops in, per-layer K / V columns out), slot lists and segments in device memory
@@ -601,6 +603,37 @@ int mmt_track_update(const float* pred_cxcywh, const double* crop, double* state
 int mmt_track_update_slots(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
                            const int32_t* hw, const uint8_t* active, int n, int search_size, double margin,
                            void* stream);
+
+/* The batched tracker's packed step: the model runs at batch n on the slots named by slot_list_dev
+ * (int32[n], DEVICE memory, read by the kernels only: nothing is allocated or read on the host, a
+ * captured launch serves every list, and the grid depends on n, never on the list's contents).
+ * A list position j is SKIPPED -- nothing is read through it, nothing is written for it -- when
+ * slot_list_dev[j] is negative or >= slots (the caller pads the list with -1).
+ *
+ * mmt_sample_target_packed: table_dev holds per_slot entries per slot (slots * per_slot in all; the
+ * batched tracker: 2, one per modality), enable_dev is NULL or one byte per table entry as in
+ * mmt_sample_target_table.  For list position j and modality m < per_slot the entry
+ * slot_list_dev[j] * per_slot + m is processed with mmt_sample_target_table's arithmetic, bit for bit, and
+ * its skip rules (applied to the entry as stored: out and patch both NULL skips it), except that the
+ * normalised crop goes to packed row j of the caller's buffer, out + m * mod_stride + j * row_stride
+ * (strides in floats, [3][out_sz][out_sz] fp32 per row), NOT to the entry's own `out`, which is neither
+ * read nor written.  The entry's crop record, and patch if set, are written through the entry's own
+ * pointers: the crop geometry stays slot-indexed.  MMT_EBADARG (before any launch): table_dev,
+ * slot_list_dev or out NULL, n <= 0, slots <= 0, per_slot outside 1..MMT_MAX_CROPS, out_sz <= 0, a
+ * negative stride, or n * per_slot * ceil(out_sz^2 / 256) blocks past the grid limit 2^31 - 1.
+ *
+ * mmt_track_update_packed: mmt_track_update_slots with prediction row pred_cxcywh[j] applied to slot
+ * s = slot_list_dev[j]: state[s], hw[s], the crop record at crop + s * crop_stride and active[s] (NULL:
+ * all slots) are the slot's own, over `slots` slots.  A position is skipped when its index is negative
+ * or >= slots, when active[s] == 0, or when H <= 0 or W <= 0; an unlisted or skipped slot's state stays
+ * bitwise unchanged.  Duplicate slots in one list are the caller's error (two rows would race on one
+ * state).  MMT_EBADARG: as mmt_track_update_slots, plus a NULL list and slots <= 0. */
+int mmt_sample_target_packed(const mmt_crop_params* table_dev, const uint8_t* enable_dev, const int32_t* slot_list_dev,
+                             int n, int slots, int per_slot, int out_sz, float* out, int64_t mod_stride,
+                             int64_t row_stride, void* stream);
+int mmt_track_update_packed(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
+                            const int32_t* hw, const uint8_t* active, const int32_t* slot_list_dev, int n, int slots,
+                            int search_size, double margin, void* stream);
 
 /* Slot-indexed row copy (the batched tracker's per-slot template K/V cache).  A segment describes one
  * strided 2-D block per slot on each side: slot s, row r occupies row_bytes bytes at

@@ -15,6 +15,10 @@
 //                       the same two for the batched tracker (N sequences per step): the crop
 //                       descriptors in a device table of any length, a frame size and an active
 //                       flag per slot.  Same device functions, same bits.
+//   mmt_sample_target_packed / mmt_track_update_packed
+//                       the batched tracker's packed step: a slot list in device memory picks the
+//                       table entries (crops go to packed row j) and the slots that prediction
+//                       row j updates.  Same device functions, same bits.
 //
 // cv2 is not part of this image, so the resize arithmetic restates OpenCV's 8-bit INTER_LINEAR
 // path (imgproc resize.cpp: float source coordinate (d+0.5)*scale-0.5, 11-bit fixed-point weights
@@ -165,6 +169,45 @@ __global__ __launch_bounds__(256) void sample_target_table_kernel(const mmt_crop
     sample_pixel(sp, sg, idx);
 }
 
+// The packed form: block b works on list position j = b / (per_slot * tiles), modality m and one
+// 256-pixel tile; its entry is slot_list[j] * per_slot + m.  The list is read here only, so the grid
+// depends on n and never on the list; a position whose index is not in [0, slots) returns before the
+// entry is read.  The entry's own `out` is replaced by packed row j of the caller's buffer; crop and
+// patch stay the entry's, so the crop geometry stays slot-indexed.
+__global__ __launch_bounds__(256) void sample_target_packed_kernel(const mmt_crop_params* __restrict__ table,
+                                                                   const uint8_t* __restrict__ enable,
+                                                                   const int32_t* __restrict__ slot_list, int slots,
+                                                                   int per_slot, int tiles, int out_sz,
+                                                                   float* __restrict__ out, int64_t mod_stride,
+                                                                   int64_t row_stride) {
+    __shared__ mmt_crop_params sp;
+    __shared__ Geo sg;
+    __shared__ int live;
+    const int pos = blockIdx.x / tiles, tile = blockIdx.x - pos * tiles;
+    const int j = pos / per_slot, m = pos - j * per_slot;
+    if (threadIdx.x == 0) {
+        const int s = slot_list[j];
+        int ok = s >= 0 && s < slots;
+        if (ok) {
+            const int64_t e = (int64_t)s * per_slot + m;
+            sp = table[e];
+            const int on = enable ? enable[e] : 1;
+            ok = on && sp.image && sp.box && (sp.out || sp.patch) && sp.H > 0 && sp.W > 0 && sp.out_sz == out_sz &&
+                 sp.factor > 0.0;
+            if (ok) {
+                sp.out = out + m * mod_stride + j * row_stride;
+                sg = crop_geometry(sp);
+            }
+        }
+        live = ok;
+    }
+    __syncthreads();
+    if (!live) return;
+    const int idx = tile * 256 + threadIdx.x;
+    if (idx >= out_sz * out_sz) return;
+    sample_pixel(sp, sg, idx);
+}
+
 // map_box_back + clip_box of one tracker: pred (cx, cy, w, h) normalised to the search crop, rf the
 // crop's resize factor, s the state (x, y, w, h) updated in place.
 MMT_DEV void track_update_one(const float* __restrict__ pred, double rf, double* __restrict__ s, int H, int W,
@@ -206,6 +249,23 @@ __global__ void track_update_slots_kernel(const float* __restrict__ pred, const 
     const int H = hw[i * 2], W = hw[i * 2 + 1];
     if (H <= 0 || W <= 0) return;
     track_update_one(pred + i * 4, crop[(int64_t)i * crop_stride + 3], state + i * 4, H, W, search_size, margin);
+}
+
+// Prediction row j updates slot slot_list[j]: state, hw, the crop record and the active byte are the
+// slot's.  A position outside [0, slots), an inactive slot or one without a frame size writes nothing.
+__global__ void track_update_packed_kernel(const float* __restrict__ pred, const double* __restrict__ crop,
+                                           int crop_stride, double* __restrict__ state, const int32_t* __restrict__ hw,
+                                           const uint8_t* __restrict__ active, const int32_t* __restrict__ slot_list,
+                                           int n, int slots, int search_size, double margin) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int s = slot_list[j];
+    if (s < 0 || s >= slots) return;
+    if (active && !active[s]) return;
+    const int H = hw[(int64_t)s * 2], W = hw[(int64_t)s * 2 + 1];
+    if (H <= 0 || W <= 0) return;
+    track_update_one(pred + (int64_t)j * 4, crop[(int64_t)s * crop_stride + 3], state + (int64_t)s * 4, H, W, search_size,
+                     margin);
 }
 
 }  // namespace
@@ -251,5 +311,31 @@ extern "C" int mmt_track_update_slots(const float* pred_cxcywh, const double* cr
     if (!pred_cxcywh || !crop || !state || !hw || n <= 0 || search_size <= 0 || crop_stride < 4) return MMT_EBADARG;
     hipLaunchKernelGGL(track_update_slots_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred_cxcywh,
                        crop, crop_stride, state, hw, active, n, search_size, margin);
+    return launch_status();
+}
+
+extern "C" int mmt_sample_target_packed(const mmt_crop_params* table_dev, const uint8_t* enable_dev,
+                                        const int32_t* slot_list_dev, int n, int slots, int per_slot, int out_sz,
+                                        float* out, int64_t mod_stride, int64_t row_stride, void* stream) {
+    if (!table_dev || !slot_list_dev || !out || n <= 0 || slots <= 0 || per_slot < 1 || per_slot > MMT_MAX_CROPS ||
+        out_sz <= 0 || out_sz > 16384)
+        return MMT_EBADARG;
+    if (mod_stride < 0 || row_stride < 0) return MMT_EBADARG;
+    const int64_t tiles = ((int64_t)out_sz * out_sz + 255) / 256;
+    if (tiles * n * per_slot > 0x7fffffff) return MMT_EBADARG;  // one block per (position, modality, 256 pixels)
+    hipLaunchKernelGGL(sample_target_packed_kernel, dim3((unsigned)(tiles * n * per_slot)), dim3(256), 0,
+                       (hipStream_t)stream, table_dev, enable_dev, slot_list_dev, slots, per_slot, (int)tiles, out_sz, out,
+                       mod_stride, row_stride);
+    return launch_status();
+}
+
+extern "C" int mmt_track_update_packed(const float* pred_cxcywh, const double* crop, int crop_stride, double* state,
+                                       const int32_t* hw, const uint8_t* active, const int32_t* slot_list_dev, int n,
+                                       int slots, int search_size, double margin, void* stream) {
+    if (!pred_cxcywh || !crop || !state || !hw || !slot_list_dev || n <= 0 || slots <= 0 || search_size <= 0 ||
+        crop_stride < 4)
+        return MMT_EBADARG;
+    hipLaunchKernelGGL(track_update_packed_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred_cxcywh,
+                       crop, crop_stride, state, hw, active, slot_list_dev, n, slots, search_size, margin);
     return launch_status();
 }

@@ -96,7 +96,8 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
         slot that fails ("Too small bounding box.") is released and reported as {"error": exception}
         in place of its box; the others go on.  mmt_amd.tracking.track_sequences drives `.core` over
         a list of sequences.  params.slot_cache / params.refresh_slots: the per-slot template K/V cache
-        (off by default); save_all_boxes and the whole-batch kv_cache are not supported here."""
+        (off by default); params.pack_slots: the packed step's batch sizes, a tuple or "auto" (off by
+        default: RGBTBatchTrackerCore's `pack`); save_all_boxes and the whole-batch kv_cache are not supported here."""
 
         def __init__(self, params, dataset_name, slots):
             if getattr(params, "save_all_boxes", False):
@@ -116,7 +117,8 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
                                              multimodal=multimodal, online_score=online_score,
                                              kv_cache=getattr(params, "kv_cache", False), slots=self.slots,
                                              slot_cache=getattr(params, "slot_cache", False),
-                                             refresh_slots=getattr(params, "refresh_slots", None))
+                                             refresh_slots=getattr(params, "refresh_slots", None),
+                                             pack=getattr(params, "pack_slots", None))
 
         def initialize(self, slot, image, info: dict):
             """image: [image_v, image_i]; info["init_bbox"]: (bbox_v, bbox_i), the RGB box is used."""

@@ -158,6 +158,8 @@ _PROTOS = {
     "mmt_track_update": [vp, vp, vp, i32, i32, i32, i32, f64, vp],
     "mmt_sample_target_table": [vp, vp, i32, i32, vp],
     "mmt_track_update_slots": [vp, vp, i32, vp, vp, vp, i32, i32, f64, vp],
+    "mmt_sample_target_packed": [vp, vp, vp, i32, i32, i32, i32, vp, i64, i64, vp],
+    "mmt_track_update_packed": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f64, vp],
     "mmt_slot_copy": [vp, i32, vp, i32, vp, i32, i32, i64, vp],
     "mmt_adamw_chunk_elems": [],
     "mmt_adamw_step": [vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f32, i32, vp],

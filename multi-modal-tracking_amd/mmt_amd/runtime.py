@@ -1086,13 +1086,65 @@ class MixFormerRGBTRuntime:
                 self.run_plan(sc["plan"])
         return len(chunks)
 
-    def plan_for_inputs(self, template, online_template, search, run_score_head=False, part=None):
+    def slot_pack_gather(self, N, R, slot_list, ws_key, template=None, online_template=None, pack_template=None,
+                         pack_online=None):
+        """The template side of the batched tracker's packed step at batch R < N: one mmt_slot_copy launch that
+        gathers the slots named by `slot_list` (int32[R] in device memory, -1 = no slot) into the batch-R
+        workspace `ws_key` -- a workspace of its own, so the rung aliases neither workspace(R), nor the slot
+        cache's staging pass, nor a caller's set_template at batch R.
+          template / online_template given (the N-slot [rgb, tir] fp32 crops): the four segments of the refresh
+            plan's gather, into pack_template / pack_online (batch-R tensors of the same row shape); the
+            workspace is workspace(R, ws_key) and runs the full forward.
+          not given: the slot cache.  Per layer and modality the n_t template rows' K and V columns, and for
+            asym_online the slots' KV1 rows, from cache_workspace(N) into cache_workspace(R, ws_key): the segment
+            geometry of slot_cache_workspace's scatter.  The batch-R cache rows are zeroed when first created
+            (a padded row is never written).
+        The gather runs every step, so the batch-R side holds no state.  Returns (ws, [launch]); the launch
+        keeps its segment table alive."""
+        N, R = int(N), int(R)
+        if not 1 <= R <= N:
+            raise ValueError("packed step needs 1 <= R <= N slots, got R=%d N=%d" % (R, N))
+        d = self.d
+        if template is not None:
+            ws = self.workspace(R, ws_key)
+            img = 3 * d.ht * d.ht * 4
+            pairs = list(zip(list(template) + list(online_template), list(pack_template) + list(pack_online)))
+            for src, dst in pairs:
+                if (tuple(src.shape) != (N, 3, d.ht, d.ht) or tuple(dst.shape) != (R, 3, d.ht, d.ht)
+                        or src.dtype != torch.float32 or dst.dtype != torch.float32 or not src.is_contiguous()
+                        or not dst.is_contiguous()):
+                    raise ValueError("packed templates must be contiguous fp32 (slots, 3, %d, %d) tensors" % (d.ht, d.ht))
+            segs = [(src, dst, img, img, img, img, 1, img) for src, dst in pairs]
+        else:
+            refuse_cache_with_ce(self.variant)
+            src_ws = self.cache_workspace(N)
+            fresh = "plan_t" not in self._ws.get(ws_key, ())
+            ws = self.cache_workspace(R, key=ws_key)
+            if fresh:
+                for q in ws["QKVL"]:
+                    q.zero_()
+                if "KV1" in ws:
+                    ws["KV1"].zero_()
+            es = ws["QKVL"][0].element_size()
+            C, ntok = d.C, d.ntok
+            row = 3 * C * es
+            segs = [(_ptr(src_ws["QKVL"][i], m * N * ntok * 3 * C + C), _ptr(ws["QKVL"][i], m * R * ntok * 3 * C + C),
+                     ntok * row, ntok * row, row, row, d.n_t, 2 * C * es)
+                    for i in range(d.depth) for m in range(d.nmod)]
+            if self.variant == "asym_online":
+                r1 = 2 * C * 4
+                segs.append((src_ws["KV1"], ws["KV1"], d.n_t * r1, d.n_t * r1, r1, r1, d.n_t, r1))
+        tab, smax = self._slot_table(segs)
+        return ws, [(LIB.mmt_slot_copy, (_ptr(tab), len(segs), _ptr(slot_list), N, None, R, R, smax), "pack_gather", tab)]
+
+    def plan_for_inputs(self, template, online_template, search, run_score_head=False, part=None, ws_key=None):
         """The plan of batch B with its patch staging reading the given device tensors directly
         (zero-copy: for frames already resident in HBM, e.g. written there by the preprocessing).
         part None: the full forward; "t": the template pass (search may be None); "s": the search
-        pass against the cache (template / online_template may be None)."""
+        pass against the cache (template / online_template may be None).  ws_key: the plan of a second,
+        separate workspace of batch B (workspace's key; default: the batch's own)."""
         B = (search if part == "s" else template)[0].shape[0]
-        ws = self.workspace(B) if part is None else self.cache_workspace(B)
+        ws = self.workspace(B, ws_key) if part is None else self.cache_workspace(B, key=ws_key)
         score = bool(run_score_head) and self.variant == "asym_online"
         key = {None: "plan", "t": "plan_t", "s": "plan_s"}[part]
         base = ws[key + "_score" if score and part != "t" else key]

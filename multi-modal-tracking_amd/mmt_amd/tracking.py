@@ -263,6 +263,46 @@ def template_schedule(online_score, frame_id, update_intervals, pred_score=None,
     return crop, due, max_pred_score
 
 
+def pack_rungs(pack, slots):
+    """The batch sizes of the packed step, ascending: `pack` None or () -> () (off); "auto" -> slots // 2,
+    slots // 4, ..., 1; else a sequence of distinct sizes R with 1 <= R < slots.  ValueError otherwise."""
+    slots = int(slots)
+    if pack is None:
+        return ()
+    if isinstance(pack, str):
+        if pack != "auto":
+            raise ValueError("pack must be None, \"auto\" or a tuple of batch sizes, got %r" % (pack,))
+        rungs, r = [], slots // 2
+        while r >= 1:
+            rungs.append(r)
+            r //= 2
+        return tuple(sorted(rungs))
+    try:
+        rungs = [r for r in pack]
+    except TypeError:
+        raise ValueError("pack must be None, \"auto\" or a tuple of batch sizes, got %r" % (pack,)) from None
+    for r in rungs:
+        if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r < slots:
+            raise ValueError("a packed batch size must be an int in 1..slots-1 (slots=%d), got %r" % (slots, r))
+    if len(set(rungs)) != len(rungs):
+        raise ValueError("duplicate packed batch size in %r" % (pack,))
+    return tuple(sorted(rungs))
+
+
+def choose_rung(rungs, n_active):
+    """The batch a step of n_active slots runs at: the smallest rung >= n_active, or None (the full step)."""
+    fit = [r for r in rungs if r >= n_active]
+    return min(fit) if fit else None
+
+
+def pack_list(active, rung):
+    """The rung's slot list: the active slots in ascending order, padded with -1 to `rung` entries."""
+    act = sorted(int(b) for b in active)
+    if len(act) > rung:
+        raise ValueError("%d active slots do not fit batch %d" % (len(act), rung))
+    return act + [-1] * (rung - len(act))
+
+
 class RGBTBatchTrackerCore:
     """`slots` sequences tracked together: one tracking step of every slot is ONE hipGraph replay of
       mmt_sample_target_table (2 * slots search crops, read from a crop-descriptor table in device memory)
@@ -272,7 +312,7 @@ class RGBTBatchTrackerCore:
     sequence ends, `assign` starts the next one in it.  The captured graph holds the table pointer,
     not the frame pointers: a new frame size rewrites the slot's table entries and keeps the graph.
 
-    Arguments as RGBTTrackerCore, plus slots, slot_cache and refresh_slots.  kv_cache (the whole-batch
+    Arguments as RGBTTrackerCore, plus slots, slot_cache, refresh_slots and pack.  kv_cache (the whole-batch
     template pass) is refused (NotImplementedError): slots update their templates on different frames;
     slot_cache is its per-slot form.
 
@@ -287,13 +327,24 @@ class RGBTBatchTrackerCore:
     every active slot.  refresh_slots defaults to min(8, slots).  refresh_replays counts the replays.
     Candidate-elimination networks raise the runtime's NotImplementedError at construction.
 
+    pack=(R, ...) or "auto" (pack_rungs; default None: off, the step above and nothing else): when the
+    active slots fit a smaller batch, the step runs at the smallest rung R >= len(active) on the active
+    slots only: mmt_sample_target_packed (search crops of the slots of a device slot list, into the rung's
+    batch-R rows) -> one mmt_slot_copy gathering the listed slots' templates (slot_cache: their K / V rows
+    of the N-slot cache) -> the model's plan at batch R in a workspace of the rung's own ->
+    mmt_track_update_packed (row j updates slot list[j]).  Each rung has its own plan and graph, built at
+    its first use; the list (active slots ascending, padded with -1) is rewritten only when the membership
+    changes; the gather runs every step, so a rung holds no state and the refreshes, dirty marks and the
+    template schedule are what they are without packing.  step_counts: {batch: steps run at it}.  After a
+    packed step of the online-score tracker last_scores is NaN for the slots that did not run.
+
     Failures: a slot whose search crop side falls below 1 (the reference's "Too small bounding
     box.") is released by `track`, and the returned mapping carries the Exception object in place of
     that slot's box; the other slots are not affected."""
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
                  multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1, slot_cache=False,
-                 refresh_slots=None):
+                 refresh_slots=None, pack=None):
         if kv_cache:
             raise NotImplementedError("kv_cache is the whole-batch template pass, the batched tracker's template "
                                       "updates are per slot: use slot_cache=True (the per-slot template K/V cache)")
@@ -301,6 +352,9 @@ class RGBTBatchTrackerCore:
             raise ValueError("slots must be >= 1")
         self.net = network
         self.slots = N = int(slots)
+        self.pack = pack_rungs(pack, N)
+        self._packs = {}  # rung -> its list, buffers, plan and graph
+        self.step_counts = {}
         self.slot_cache = bool(slot_cache)
         self.refresh_slots = min(8, N) if refresh_slots is None else int(refresh_slots)
         if self.slot_cache and not 1 <= self.refresh_slots <= N:
@@ -427,20 +481,78 @@ class RGBTBatchTrackerCore:
         else:
             self._graph = None
 
+    def _build_pack(self, rt, R):
+        """Rung R's slot list, batch-R inputs, launch plan and (at its first step) graph."""
+        N, dev = self.slots, self.dev
+        z = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        pk = {"R": R, "members": None, "graph": None,
+              "list": torch.full((R,), -1, device=dev, dtype=torch.int32),
+              "search": z(2, R, 3, self.ss, self.ss)}  # one buffer: [modality][row], the packed crop's two strides
+        search = [pk["search"][0], pk["search"][1]]
+        key = ("pack", N, R)
+        if self.slot_cache:
+            ws, gather = rt.slot_pack_gather(N, R, pk["list"], key)
+            model_plan = rt.plan_for_inputs(None, None, search, run_score_head=self.online_score, part="s", ws_key=key)
+        else:
+            pk["template"] = [z(R, 3, self.ts, self.ts) for _ in range(2)]
+            pk["online_template"] = [z(R, 3, self.ts, self.ts) for _ in range(2)]
+            ws, gather = rt.slot_pack_gather(N, R, pk["list"], key, self.template, self.online_template,
+                                             pk["template"], pk["online_template"])
+            model_plan = rt.plan_for_inputs(pk["template"], pk["online_template"], search,
+                                            run_score_head=self.online_score, ws_key=key)
+        row = 3 * self.ss * self.ss
+        plan = [(LIB.mmt_sample_target_packed, (self._search_tab.data_ptr(), self._search_enable.data_ptr(),
+                                                pk["list"].data_ptr(), R, N, 2, self.ss, pk["search"].data_ptr(), R * row, row),
+                 "track_sample_target_packed", None)]
+        plan += gather
+        plan += model_plan
+        plan.append((LIB.mmt_track_update_packed, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), 8, self.state.data_ptr(),
+                                                   self.hw.data_ptr(), self.active.data_ptr(), pk["list"].data_ptr(), R, N,
+                                                   self.ss, 10.0),
+                     "track_update_packed", None))
+        pk["ws"], pk["plan"] = ws, plan
+        return pk
+
     def _step(self):
-        if self._plan is not None and self.net._runtime(self.dev) is not self._rt:
+        """Runs one step; returns the packed rung's state, or None after the full step."""
+        rt = self.net._runtime(self.dev)
+        if (self._plan is not None or self._packs) and rt is not self._rt:
             self._graph = self._plan = None  # weights reloaded: re-plan, re-capture
+            self._packs = {}
             if self.slot_cache:  # the new runtime's cache holds none of the templates
                 self._dirty.update(self._act)
-        if self._plan is None or (self.use_graph and self._graph is None):
-            self._build_step()
+        R = choose_rung(self.pack, len(self._act)) if self.pack else None
+        if R is None:
+            if self._plan is None or (self.use_graph and self._graph is None):
+                self._build_step()
+            pk, graph, plan = None, self._graph, self._plan
+        else:
+            if self._rt is not rt or (self.slot_cache and self._sc is None):
+                self._rt = rt
+                if self.slot_cache:
+                    self._sc = self._slot_state(rt)
+            pk = self._packs.get(R)
+            if pk is None:
+                pk = self._packs[R] = self._build_pack(rt, R)
+            if pk["members"] != self._act:
+                pk["list"].copy_(torch.tensor(pack_list(self._act, R), dtype=torch.int32))
+                pk["members"] = list(self._act)
         if self._dirty:  # slot cache: template pass of the slots whose templates changed
             self.refresh_replays += self._rt.refresh_template_slots(self._sc, sorted(self._dirty), self.use_graph)
             self._dirty.clear()
-        if self._graph is not None:
-            self._graph.replay()
+        if pk is not None:
+            if self.use_graph and pk["graph"] is None:
+                saved = self.state.clone()  # capture_plan runs the plan once: keep this frame's states
+                pk["graph"] = self._rt.capture_plan(pk["plan"])
+                self.state.copy_(saved)
+            graph, plan = pk["graph"], pk["plan"]
+        if graph is not None:
+            graph.replay()
         else:
-            self._rt.run_plan(self._plan)
+            self._rt.run_plan(plan)
+        B = self.slots if pk is None else pk["R"]
+        self.step_counts[B] = self.step_counts.get(B, 0) + 1
+        return pk
 
     # ------------------------------------------------------------------ tracker API
     def active_slots(self):
@@ -487,12 +599,17 @@ class RGBTBatchTrackerCore:
         for b in act:
             self._load_frames(b, images[b])
             self.frame_id[b] += 1
-        self._step()
+        pk = self._step()
         N = self.slots
         parts = self._readback
         if self.online_score:
-            parts = parts + [torch.sigmoid(self._ws["SC"].view(-1)).double()]
+            parts = parts + [torch.sigmoid((self._ws if pk is None else pk["ws"])["SC"].view(-1)).double()]
         vals = torch.cat(parts).tolist()  # the step's one host round trip, for all slots
+        if self.online_score and pk is not None:  # the rung's rows back to their slots
+            scores = [float("nan")] * N
+            for j, b in enumerate(act):
+                scores[b] = vals[5 * N + j]
+            vals[5 * N:] = scores
         out, crop, promote = {}, [], []
         for b in act:
             if vals[4 * N + b] < 1:

@@ -24,7 +24,18 @@ bytes/s, read + written.  With --trace-run the cached side is traced, and --kern
 mmt_slot_copy's launches by grid from the per-dispatch trace beside the stats file (the stats file sums the gather
 and the scatter under one kernel name) and gives the scatter's bytes/s inside the refresh plan.
 
-    python tools/batch_tracker_time.py --slot-cache --out profiles/batch_tracker_time.jsonl"""
+    python tools/batch_tracker_time.py --slot-cache --out profiles/batch_tracker_time.jsonl
+
+--pack: the packed step (RGBTBatchTrackerCore(pack="auto")) on 64 slots with --active of them holding a sequence,
+same protocol, three sides alternating: the packing core, the same core with pack off, and a core of slots = R (the
+rung the packed step runs at) holding the same sequences.  The record carries the three rates, the step times, the
+packed step's excess over the slots = R core, the run's own spread, and the device time of the launches the packed
+step adds (packed crop, template gather, packed update: each alone between two device events), plus the bytes a rung
+owns.  With --slot-cache all three cores use the per-slot cache.  --drain: track_sequences over 128 sequences of
+long-tailed lengths (fixed seed, written into the record) on 64 slots, wall time and step_counts with pack="auto" and
+with pack off (each side includes the capture of its graphs).
+
+    python tools/batch_tracker_time.py --pack --drain --variants shared [--slot-cache]"""
 import argparse
 import csv
 import json
@@ -78,6 +89,9 @@ def main():
     ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--slot-cache", action="store_true")
     ap.add_argument("--refresh-slots", type=int, default=0, help="refresh capacity (0: the core's default)")
+    ap.add_argument("--pack", action="store_true", help="the packed step: see the module docstring")
+    ap.add_argument("--active", default="64,33,32,8,1", help="--pack: active slots of the 64 (empty: none)")
+    ap.add_argument("--drain", action="store_true", help="--pack: also the 128-sequence drain")
     args = ap.parse_args()
     out = open(args.out, "a")
 
@@ -201,6 +215,128 @@ def main():
             return
         _, step_b, _ = sides(network(variant), variant, args.trace_run)
         timed(step_b, 30)
+        return
+
+    def pack_sides(net, variant, N, A, cached):
+        """(p) the packing core with A of N slots active, (o) the same core with pack off, (r) a core of
+        slots = R -- the rung the packed step runs at, N when there is none -- holding the same A sequences."""
+        from mmt_amd.tracking import choose_rung, pack_rungs
+        mm = builders[variant][1]
+        R = choose_rung(pack_rungs("auto", N), A) or N
+        act = [i * N // A for i in range(A)]  # spread over the slots, ascending
+        kw = dict(multimodal=mm, slot_cache=cached)
+        cores = [RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], slots=N, pack="auto",
+                                      refresh_slots=(args.refresh_slots or None) if cached else None, **kw),
+                 RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], slots=N,
+                                      refresh_slots=(args.refresh_slots or None) if cached else None, **kw),
+                 RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], slots=R,
+                                      refresh_slots=(min(args.refresh_slots, R) or None) if cached else None, **kw)]
+        where = [act, act, list(range(A))]
+        steps = []
+        for c, slots in zip(cores, where):
+            for k, b in enumerate(slots):
+                c.assign(b, frames[0], init_box(k))
+            init = c.state.clone()
+
+            def step(i, c=c, slots=slots, init=init):
+                c.state.copy_(init)
+                r = c.track({b: frames[(i + k) % 4] for k, b in enumerate(slots)})
+                assert len(r) == A and not any(isinstance(v, Exception) for v in r.values())
+            steps.append(step)
+        return R, cores, steps
+
+    def pack_launch_times(core, R):
+        """Device time of the launches a packed step adds to the batch-R plan: the packed crop, the template gather
+        and the packed update, each alone between two device events (50 launches after 3)."""
+        pk = core._packs[R]
+        st = torch.cuda.current_stream().cuda_stream
+        saved = core.state.clone()
+        out = {}
+        for fn, a, name, _ in (pk["plan"][0], pk["plan"][1], pk["plan"][-1]):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            for _ in range(3):
+                fn(*a, st)
+            ev[0].record()
+            for _ in range(50):
+                fn(*a, st)
+            ev[1].record()
+            torch.cuda.synchronize()
+            out[name + "_us"] = round(ev[0].elapsed_time(ev[1]) * 1e3 / 50, 2)
+        core.state.copy_(saved)
+        seen, total = set(), 0
+        for v in list(pk.values()) + list(pk["ws"].values()):
+            for t in (v if isinstance(v, (list, tuple)) else [v]):
+                if isinstance(t, torch.Tensor) and t.data_ptr() not in seen:
+                    seen.add(t.data_ptr())
+                    total += t.numel() * t.element_size()
+        out["rung_bytes"] = total
+        return out
+
+    def drain_lengths(n=128, seed=7):
+        """Long-tailed sequence lengths (frames, the first one included) from a fixed seed."""
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        return [int(v) for v in np.clip(8 + 24 * rng.pareto(1.1, n), 8, 1000).astype(int)]
+
+    if args.pack:
+        from mmt_amd.tracking import track_sequences
+        for variant in args.variants.split(","):
+            net = network(variant)
+            N = 64
+            for A in [int(x) for x in args.active.split(",") if x]:
+                R, cores, steps = pack_sides(net, variant, N, A, args.slot_cache)
+                names = ("packed_core", "pack_off_core", "small_core")
+                n = []
+                for step in steps:
+                    timed(step, 3)
+                    n.append(max(5, int(args.seconds / (timed(step, 5) / 5)) + 1))
+                rates = [[] for _ in steps]
+                for _ in range(args.repeats):
+                    for k, step in enumerate(steps):
+                        rates[k].append(A * n[k] / timed(step, n[k]))
+                rec = {"what": "tracker_step_packed", "variant": variant, "slots": N, "active": A, "batch": R,
+                       "slot_cache": bool(args.slot_cache), "dtype": "bf16", "frame": [H, W], "steps": dict(zip(names, n)),
+                       "update_interval": INTERVAL, "unit": "sequence-frames/s", "step_counts": {
+                           k: {str(b): v for b, v in c.step_counts.items()} for k, c in zip(names, cores)}}
+                for k, key in enumerate(names):
+                    r = sorted(rates[k])
+                    rec[key] = {"median": round(r[len(r) // 2], 1), "min": round(r[0], 1), "max": round(r[-1], 1)}
+                ms = lambda key, q: 1e3 * A / rec[key][q]  # noqa: E731  step time in ms
+                rec["step_ms"] = {key: round(ms(key, "median"), 4) for key in names}
+                rec["packed_minus_small_ms"] = round(ms("packed_core", "median") - ms("small_core", "median"), 4)
+                rec["spread_ms"] = round((ms("packed_core", "min") - ms("packed_core", "max"))
+                                         + (ms("small_core", "min") - ms("small_core", "max")), 4)
+                if R < N:
+                    rec.update(pack_launch_times(cores[0], R))
+                    rec["added_launches_ms"] = round((rec["track_sample_target_packed_us"] + rec["pack_gather_us"]
+                                                      + rec["track_update_packed_us"]) / 1e3, 4)
+                    rec["within_margin"] = rec["packed_minus_small_ms"] <= rec["spread_ms"] + rec["added_launches_ms"]
+                else:  # full occupancy or no rung: the packing core and the pack-off core replay the same graph
+                    rec["within_margin"] = abs(ms("packed_core", "median") - ms("pack_off_core", "median")) <= rec["spread_ms"]
+                emit(rec)
+                del cores, steps
+                torch.cuda.empty_cache()
+            if args.drain:
+                lengths = drain_lengths()
+                rec = {"what": "tracker_drain", "variant": variant, "slots": N, "slot_cache": bool(args.slot_cache),
+                       "dtype": "bf16", "frame": [H, W], "update_interval": INTERVAL, "sequences": len(lengths),
+                       "lengths_seed": 7, "lengths": lengths, "tracked_frames": sum(lengths) - len(lengths)}
+                for key, pack in (("pack_auto", "auto"), ("pack_off", None)):
+                    core = RGBTBatchTrackerCore(net, 2.0, 128, 5.0, 320, [INTERVAL], multimodal=builders[variant][1],
+                                                slots=N, slot_cache=args.slot_cache, pack=pack,
+                                                refresh_slots=(args.refresh_slots or None) if args.slot_cache else None)
+                    seqs = [("q%d" % k, (frames[(k + i) % 4] for i in range(L)), init_box(k)) for k, L in enumerate(lengths)]
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    res = track_sequences(core, seqs)
+                    wall = time.perf_counter() - t0
+                    assert all(len(res["q%d" % k]) == L for k, L in enumerate(lengths))
+                    rec[key] = {"wall_s": round(wall, 3), "step_counts": {str(b): v for b, v in sorted(core.step_counts.items())},
+                                "sequence_frames_per_s": round(rec["tracked_frames"] / wall, 1)}
+                    del core
+                    torch.cuda.empty_cache()
+                rec["speedup"] = round(rec["pack_off"]["wall_s"] / rec["pack_auto"]["wall_s"], 3)
+                emit(rec)
         return
 
     if args.slot_cache:
