@@ -22,14 +22,15 @@ three launches over every parameter, writing the bf16 copies of the backbone wei
 read).  The backbone LayerNorms run on mmt_layernorm / mmt_layernorm_bwd (_HipLayerNorm), and each
 block's MLP is one autograd Function whose GELU and GELU backward live in GEMM epilogues (_HipMlp).  The Linear
 Functions (_HipLinear, _HipLinearResidual, _HipMlp) are generic over the group count: one (weight, bias) set for
-one backbone or stream, two for the RGB / TIR backbones in lockstep on stacked rows (grouped GEMMs).  The
-fusion encoder's LayerNorms take the same kernels, and the fusion's adjust_* 1x1 convs + GroupNorms run on
-token rows as the HIP GEMM + mmt_groupnorm / mmt_groupnorm_bwd.  The residual adds and the corner head run as
-PyTorch-ROCm ops on the same
-module tree (`nn.Conv2d`, `nn.GroupNorm`, `SyncBatchNorm` under DDP), in bf16 autocast like the
-reference's AMP path.  The backbone ops are injected (`ops`), so the data-parallel plumbing can be exercised on CPU
+one backbone or stream, two for the RGB / TIR backbones in lockstep on stacked rows (grouped GEMMs); the forward
+above them is one block loop too (_vit_forward), behind backbone_forward, backbone_forward_pair and
+backbone_forward_stacked.  The fusion encoder's LayerNorms take the same kernels, and the fusion's adjust_* 1x1
+convs + GroupNorms run on token rows as the HIP GEMM + mmt_groupnorm / mmt_groupnorm_bwd.  The residual adds and
+the corner head run as PyTorch-ROCm ops on the same module tree (`nn.Conv2d`, `nn.GroupNorm`, `SyncBatchNorm`
+under DDP), in bf16 autocast like the reference's AMP path.  The backbone ops are injected (`ops`), so the data-parallel plumbing can be exercised on CPU
 with stand-in ops in tests; the product's ops are `HipOps` and have no CPU path.
 """
+import contextlib
 import math
 import time
 
@@ -1494,7 +1495,7 @@ class HipOps:
         training = bn.training or not bn.track_running_stats
         update = bn.training and bn.track_running_stats
         if update:
-            if _BN_TRACKED is not None:  # head_forward_nhwc: one multi-tensor add for the whole head
+            if _BN_TRACKED is not None:  # _bn_tracked: one multi-tensor add for the whole head / fusion
                 _BN_TRACKED.append(bn.num_batches_tracked)
             else:
                 bn.num_batches_tracked.add_(1)
@@ -1620,21 +1621,35 @@ def _keeps(x, ps, training):
     return out
 
 
-def _branch_residual(ops, x, a, lin, p, training):
-    """x + DropPath(lin(a)) for the block's attention projection: one fused GEMM with HipOps."""
+# The next three take a list of one module, or of two: the RGB / TIR backbones' in lockstep, each on its half of the
+# rows through the ops' grouped method (ops.linear2 ..., which has no fallback).
+def _lin(ops, x, lins, out_f32=False):
+    """Linear of x's rows; a conv's weight as [Cout][Cin kh kw] (the patch embed on unfolded patches)."""
+    wb = [t for m in lins for t in (m.weight.flatten(1), m.bias)]
+    return (ops.linear if len(lins) == 1 else ops.linear2)(x, *wb, out_f32=out_f32)
+
+
+def _branch_residual(ops, x, a, lins, training, p, keep=None):
+    """x + DropPath(lin(a)) for the block's attention projection: one fused GEMM with HipOps.  One module: the scale
+    is drawn here at rate p (_keep, or _residual's); two: keep is the pair's [2B] or None, drawn ahead (_keeps)."""
+    wb = [t for m in lins for t in (m.weight, m.bias)]
+    if len(lins) == 2:
+        return ops.linear_residual2(x, a, *wb, keep)
     fn = getattr(ops, "linear_residual", None)
     if fn is not None:
-        return fn(x, a, lin.weight, lin.bias, _keep(x, p, training))
-    B, ntok, C = x.shape
-    return _residual(x, ops.linear(a, lin.weight, lin.bias, out_f32=True).view(B, ntok, C), p, training)
+        return fn(x, a, *wb, _keep(x, p, training))
+    return _residual(x, ops.linear(a, *wb, out_f32=True).view(x.shape), p, training)
 
 
-def _mlp_residual(ops, x, xn, mlp, p, training):
-    """x + DropPath(Mlp(xn)): one fused autograd node with HipOps."""
+def _mlp_residual(ops, x, xn, mlps, training, p, keep=None):
+    """x + DropPath(Mlp(xn)): one fused autograd node with HipOps; p / keep as _branch_residual's."""
+    wb = [(m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias) for m in mlps]
+    if len(mlps) == 2:
+        return ops.mlp_residual2(x, xn, wb[0], wb[1], keep)
     fn = getattr(ops, "mlp_residual", None)
     if fn is not None:
-        return fn(x, xn, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias, _keep(x, p, training))
-    return _residual(x, _mlp(ops, xn, mlp).view(x.shape), p, training)
+        return fn(x, xn, *wb[0], _keep(x, p, training))
+    return _residual(x, _mlp(ops, xn, mlps[0]).view(x.shape), p, training)
 
 
 def _patches(x, p=16):
@@ -1646,68 +1661,24 @@ def _patches(x, p=16):
 
 
 def backbone_forward(bb, t, o, s, ops, drop_path_rate=DROP_PATH_RATE):
-    """VisionTransformer.forward (mixformer.py:231-259) for one modality: returns the search
-    features (B, C, gs, gs) fp32.  Tokens [template | online | search], pre-LN blocks; in training
-    mode the blocks' residual branches use stochastic depth (mixformer.py:129-138)."""
-    B = t.shape[0]
-    C = bb.pos_embed_s.shape[-1]
-    H = C // 64
-    gt, gs = bb.grid_size_t, bb.grid_size_s
-    ntok, n_t = 2 * gt * gt + gs * gs, 2 * gt * gt
-    patches = torch.cat([_patches(x) for x in (t, o, s)], 1)  # (B, ntok, 3*256)
-    w = bb.patch_embed.proj.weight
-    x = ops.linear(patches.reshape(B * ntok, -1).to(ops.dtype), w.reshape(w.shape[0], -1), bb.patch_embed.proj.bias,
-                   out_f32=True)
-    pos = torch.cat([bb.pos_embed_t, bb.pos_embed_t, bb.pos_embed_s], 1)
-    x = x.view(B, ntok, C) + pos
-    depth = len(bb.blocks)
-    for li, blk in enumerate(bb.blocks):
-        dp = drop_path_rate * li / max(depth - 1, 1)
-        xn, xr = _layer_norm_pass(ops, x, blk.norm1)
-        qkv = ops.linear(xn.view(B * ntok, C), blk.attn.qkv.weight, blk.attn.qkv.bias).view(B, ntok, 3 * C)
-        a = ops.mam_attention(qkv, n_t, H).view(B * ntok, C)
-        x = _branch_residual(ops, xr, a, blk.attn.proj, dp, bb.training)
-        xn, xr = _layer_norm_pass(ops, x, blk.norm2)
-        x = _mlp_residual(ops, xr, xn.view(B * ntok, C), blk.mlp, dp, bb.training)
-    xs = x[:, n_t:]
-    return xs.transpose(1, 2).reshape(B, C, gs, gs)
+    """VisionTransformer.forward (mixformer.py:231-259) for one modality (_vit_forward with one weight set and the
+    backbone's own norms): returns the search features (B, C, gs, gs) fp32.  In training mode the blocks' residual
+    branches use stochastic depth (mixformer.py:129-138), a draw over [B] per live branch."""
+    x, n_t = _vit_forward((bb,), t, o, s, ops, drop_path_rate)
+    return _search_maps(x, n_t, bb.grid_size_s)
 
 
 def backbone_forward_pair(bv, bi, t, o, s, ops, drop_path_rate=DROP_PATH_RATE, tokens=False):
     """backbone_forward of the two-stream model's RGB (bv) and TIR (bi) backbones in lockstep, the
     modalities stacked on the batch ([rgb; tir], t / o / s pairs of (B, 3, H, W)): the same math per
-    modality (mixformer.py:231-259, own weights, own norms, own DropPath draws), but every Linear and
-    every gradient GEMM one grouped launch for both, and one attention / LayerNorm launch over 2B
-    sequences.  Returns (s_v, s_i), each (B, C, gs, gs) fp32."""
-    B = t[0].shape[0]
-    C = bv.pos_embed_s.shape[-1]
-    H = C // 64
-    gt, gs = bv.grid_size_t, bv.grid_size_s
-    ntok, n_t = 2 * gt * gt + gs * gs, 2 * gt * gt
-    patches = torch.cat([_patches(torch.cat(x, 0)) for x in (t, o, s)], 1)  # (2B, ntok, 3*256)
-    wv, wi = bv.patch_embed.proj.weight, bi.patch_embed.proj.weight
-    x = ops.linear2(patches.reshape(2 * B * ntok, -1).to(ops.dtype), wv.reshape(wv.shape[0], -1),
-                    bv.patch_embed.proj.bias, wi.reshape(wi.shape[0], -1), bi.patch_embed.proj.bias, out_f32=True)
-    pos = torch.stack([torch.cat([bb.pos_embed_t, bb.pos_embed_t, bb.pos_embed_s], 1) for bb in (bv, bi)], 0)
-    x = (x.view(2, B, ntok, C) + pos).view(2 * B, ntok, C)
-    depth = len(bv.blocks)
-    M2 = 2 * B * ntok
-    keeps = _keeps(x, [drop_path_rate * (i // 2) / max(depth - 1, 1) for i in range(2 * depth)], bv.training)
-    for li, (kv, ki) in enumerate(zip(bv.blocks, bi.blocks)):
-        keep = keeps[2 * li]
-        xn, xr = _layer_norm_pass(ops, x, kv.norm1, ki.norm1)
-        qkv = ops.linear2(xn.view(M2, C), kv.attn.qkv.weight, kv.attn.qkv.bias, ki.attn.qkv.weight,
-                          ki.attn.qkv.bias).view(2 * B, ntok, 3 * C)
-        a = ops.mam_attention(qkv, n_t, H).view(M2, C)
-        x = ops.linear_residual2(xr, a, kv.attn.proj.weight, kv.attn.proj.bias, ki.attn.proj.weight,
-                                 ki.attn.proj.bias, keep)
-        keep = keeps[2 * li + 1]
-        xn, xr = _layer_norm_pass(ops, x, kv.norm2, ki.norm2)
-        mp = [(k.mlp.fc1.weight, k.mlp.fc1.bias, k.mlp.fc2.weight, k.mlp.fc2.bias) for k in (kv, ki)]
-        x = ops.mlp_residual2(xr, xn.view(M2, C), mp[0], mp[1], keep)
-    if tokens:  # the search tokens as bf16 rows (2B, ns, C), RGB first, for the fusion's token-row adjust
+    modality (mixformer.py:231-259, own weights, own norms, own DropPath scales, all drawn at once as one
+    [live branches][2B] bernoulli), but every Linear and every gradient GEMM one grouped launch for both, and one
+    attention / LayerNorm launch over 2B sequences.  Returns (s_v, s_i), each (B, C, gs, gs) fp32; tokens: (the
+    search tokens as bf16 rows (2B, ns, C), RGB first, for the fusion's token-row adjust; None)."""
+    x, n_t = _vit_forward((bv, bi), *(torch.cat(u, 0) for u in (t, o, s)), ops, drop_path_rate)
+    if tokens:
         return _HipSearchTokens.apply(x, n_t), None
-    xs = x[:, n_t:].transpose(1, 2).reshape(2 * B, C, gs, gs)
+    xs, B = _search_maps(x, n_t, bv.grid_size_s), t[0].shape[0]
     return xs[:B], xs[B:]
 
 
@@ -1797,37 +1768,48 @@ def _ce_stage(ops, qkv, gidx, Bh, n_t, heads, keep, N, mask, forced, trace):
     return order, gnew
 
 
-def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_PATH_RATE, ce=None,
-                             ce_template_mask=None, ce_keep_rate=None, ce_forced=None, ce_trace=None):
-    """Shared-backbone forward with the modalities stacked on the batch ([rgb; tir], 2B):
-    mixformer_shared.py:143-159, :253-282 (per-modality LayerNorms, shared weights, standard MAM) or,
-    asym, asymmetric_shared.py:137-154, :236-266 (cross-modal MAM).  Returns the search features
-    (2B, C, gs, gs) and the first template's tokens (2B, gt*gt, C) (the score decoder's memory).
+def _vit_forward(bbs, t, o, s, ops, drop_path_rate, asym=False, modal_norms=False, ce=None, ce_template_mask=None,
+                 ce_keep_rate=None, ce_forced=None, ce_trace=None):
+    """The MixFormer ViT training forward (mixformer.py:231-259) behind the three backbone_forward* wrappers.  bbs: one
+    backbone, or the RGB and TIR ones whose weight sets take the two halves of the rows (grouped Linears: _lin);
+    t / o / s (rows, 3, H, W) already stacked.  Returns (the final fp32 token stream (rows, ntok, C), n_t).
+
+    Patches unfolded and embedded as one GEMM, tokens [template | online | search] plus the position tables, then
+    the pre-LN blocks: LayerNorm (handing x on to the residual op), qkv, MAM attention (asym: the cross-modal one
+    over [rgb; tir] rows), x + DropPath(proj), LayerNorm, x + DropPath(Mlp) (mixformer.py:129-139).  A block's norms:
+    each backbone's own; modal_norms (the shared backbone): model.layer_norms' RGB / TIR norms on the two halves of
+    the rows.  DropPath (training mode, timm's linear per-block schedule, rate 0 draws nothing): two backbones take
+    their scales from one _keeps draw over [live branches][rows] before the loop, one backbone draws per branch,
+    attention then MLP in block order (_keep over [rows], or _residual's (rows, 1, 1)).
 
     ce = {block: keep ratio}: candidate elimination (asymmetric_shared_ce.py CE_Block_Shared.forward :247-282,
-    VisionTransformer.forward :372-424).  After the attention residual of an eliminating block -- its ratio
-    < 1 and ce_keep_rate None or < 1 (:250-253); a given ce_keep_rate replaces every ratio (:270) -- the
-    search tokens of both modalities are pruned to math.ceil(ratio * lens) (:77-79; nothing happens when that
-    equals lens) by the template queries' mean attention (ce_template_mask (B, 2 n_t): over the masked
-    queries), kept in sorted order after the template tokens.  The fp32 stream stays packed (2B, n_t + lens,
-    C) and shrinks at every stage; gidx (2B, lens) int32 carries the survivors' original positions, and after
-    the last block they go back there, pruned positions as zero rows (_recover_search :426-447).  Pruning,
-    recovery and their backwards are all one indexed row copy (ops.ce_rows_gather); the scores carry no
-    gradient (_ce_stage).  ce_forced / ce_trace: test hooks (per stage a pair of (B, keep) original positions
-    to keep / a list receiving each stage's ((gidx_v, gidx_i), attn_mean))."""
-    B2 = t.shape[0]
-    Bh = B2 // 2
+    VisionTransformer.forward :372-424; one backbone, asym).  After the attention residual of an eliminating
+    block -- its ratio < 1 and ce_keep_rate None or < 1 (:250-253); a given ce_keep_rate replaces every ratio
+    (:270) -- the search tokens of both modalities are pruned to math.ceil(ratio * lens) (:77-79; nothing happens
+    when that equals lens) by the template queries' mean attention (ce_template_mask (B, 2 n_t): over the masked
+    queries), kept in sorted order after the template tokens.  The fp32 stream stays packed (2B, n_t + lens, C) and
+    shrinks at every stage; gidx (2B, lens) int32 carries the survivors' original positions, and after the last
+    block they go back there, pruned positions as zero rows (_recover_search :426-447).  Pruning, recovery and
+    their backwards are all one indexed row copy (ops.ce_rows_gather); the scores carry no gradient (_ce_stage).
+    ce_forced / ce_trace: test hooks (per stage a pair of (B, keep) original positions to keep / a list receiving
+    each stage's ((gidx_v, gidx_i), attn_mean))."""
+    G, bb = len(bbs), bbs[0]
+    rows = t.shape[0]
+    Bh = rows // 2
     C = bb.pos_embed_s.shape[-1]
     H = C // 64
     gt, gs = bb.grid_size_t, bb.grid_size_s
     ntok, n_t = 2 * gt * gt + gs * gs, 2 * gt * gt
-    patches = torch.cat([_patches(x) for x in (t, o, s)], 1)
-    w = bb.patch_embed.proj.weight
-    x = ops.linear(patches.reshape(B2 * ntok, -1).to(ops.dtype), w.reshape(w.shape[0], -1), bb.patch_embed.proj.bias,
-                   out_f32=True)
-    pos = torch.cat([bb.pos_embed_t, bb.pos_embed_t, bb.pos_embed_s], 1)
-    x = x.view(B2, ntok, C) + pos
-    depth = len(bb.blocks)
+    patches = torch.cat([_patches(x) for x in (t, o, s)], 1)  # (rows, ntok, 3*256)
+    x = _lin(ops, patches.reshape(rows * ntok, -1).to(ops.dtype), [b.patch_embed.proj for b in bbs], out_f32=True)
+    pos = [torch.cat([b.pos_embed_t, b.pos_embed_t, b.pos_embed_s], 1) for b in bbs]
+    if G == 1:
+        x = x.view(rows, ntok, C) + pos[0]
+    else:
+        x = (x.view(G, rows // G, ntok, C) + torch.stack(pos, 0)).view(rows, ntok, C)
+    depth, training = len(bb.blocks), bb.training
+    dps = [drop_path_rate * (i // 2) / max(depth - 1, 1) for i in range(2 * depth)]  # per residual branch
+    drop = zip(dps, _keeps(x, dps, training) if G == 2 else [None] * len(dps))  # (rate, scale drawn ahead) in order
     if ce and ce_keep_rate is not None and ce_keep_rate >= 1:
         ce = None
     if ce and not asym:
@@ -1836,16 +1818,16 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
         ce_template_mask = ce_template_mask.to(device=x.device, dtype=torch.uint8).contiguous()
     gidx, stage, n = None, 0, ntok  # n: rows per sequence of the packed stream
 
-    def ln2(x, a, b):  # norm*_v on the RGB half, norm*_i on the TIR half (and x passed through)
-        return _layer_norm_pass(ops, x, a, b)
+    def head():  # the template rows of a gather index: themselves
+        return _const(("ce_head", rows, n_t), x.device, lambda: torch.arange(n_t, dtype=torch.int32).repeat(rows, 1))
 
-    for li, blk in enumerate(bb.blocks):
-        dp = drop_path_rate * li / max(depth - 1, 1)
-        n1, n2 = layer_norms(blk)  # one module twice in the uni-backbone's plain blocks
-        xn, xr = ln2(x, *n1)
-        qkv = ops.linear(xn.view(B2 * n, C), blk.attn.qkv.weight, blk.attn.qkv.bias).view(B2, n, 3 * C)
+    for li, blks in enumerate(zip(*(b.blocks for b in bbs))):
+        # layer_norms: one module twice in the uni-backbone's plain blocks; else one norm per backbone
+        n1, n2 = layer_norms(blks[0]) if modal_norms else zip(*((k.norm1, k.norm2) for k in blks))
+        xn, xr = _layer_norm_pass(ops, x, *n1)
+        qkv = _lin(ops, xn.view(rows * n, C), [k.attn.qkv for k in blks]).view(rows, n, 3 * C)
         a = ops.mam_attention_asym(qkv, Bh, n_t, H) if asym else ops.mam_attention(qkv, n_t, H)
-        x = _branch_residual(ops, xr, a.reshape(B2 * n, C), blk.attn.proj, dp, bb.training)
+        x = _branch_residual(ops, xr, a.reshape(rows * n, C), [k.attn.proj for k in blks], training, *next(drop))
         if ce and li in ce:
             ratio = ce[li] if ce_keep_rate is None else ce_keep_rate
             lens = n - n_t
@@ -1853,17 +1835,33 @@ def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_P
             if ratio < 1 and keep != lens:
                 order, gidx = _ce_stage(ops, qkv, gidx, Bh, n_t, H, keep, gs * gs, ce_template_mask,
                                         ce_forced[stage] if ce_forced is not None else None, ce_trace)
-                head = _const(("ce_head", B2, n_t), x.device,
-                              lambda: torch.arange(n_t, dtype=torch.int32).repeat(B2, 1))
-                x = _ce_rows_gather(ops, x, torch.cat([head, order.to(torch.int32) + n_t], 1))
+                x = _ce_rows_gather(ops, x, torch.cat([head(), order.to(torch.int32) + n_t], 1))
                 n = n_t + keep
             stage += 1
-        xn, xr = ln2(x, *n2)
-        x = _mlp_residual(ops, xr, xn.view(B2 * n, C), blk.mlp, dp, bb.training)
+        xn, xr = _layer_norm_pass(ops, x, *n2)
+        x = _mlp_residual(ops, xr, xn.view(rows * n, C), [k.mlp for k in blks], training, *next(drop))
     if gidx is not None:  # _recover_search: row n_t + gidx[j] of the full stream is row n_t + j, zeros elsewhere
-        head = _const(("ce_head", B2, n_t), x.device, lambda: torch.arange(n_t, dtype=torch.int32).repeat(B2, 1))
-        x = _ce_rows_gather(ops, x, _ce_index_invert(ops, torch.cat([head, gidx + n_t], 1), ntok))
-    return x[:, n_t:].transpose(1, 2).reshape(B2, C, gs, gs), x[:, :gt * gt]
+        x = _ce_rows_gather(ops, x, _ce_index_invert(ops, torch.cat([head(), gidx + n_t], 1), ntok))
+    return x, n_t
+
+
+def _search_maps(x, n_t, gs):
+    """The search tokens of the stream (rows, ntok, C) as maps (rows, C, gs, gs)."""
+    return x[:, n_t:].transpose(1, 2).reshape(x.shape[0], x.shape[2], gs, gs)
+
+
+def backbone_forward_stacked(bb, t, o, s, ops, asym=False, drop_path_rate=DROP_PATH_RATE, ce=None,
+                             ce_template_mask=None, ce_keep_rate=None, ce_forced=None, ce_trace=None):
+    """Shared-backbone forward with the modalities stacked on the batch ([rgb; tir], 2B):
+    mixformer_shared.py:143-159, :253-282 (per-modality LayerNorms, shared weights, standard MAM) or,
+    asym, asymmetric_shared.py:137-154, :236-266 (cross-modal MAM); ce and the ce_* arguments: candidate
+    elimination (asymmetric_shared_ce.py), as _vit_forward describes.  DropPath: a draw over [2B] per live branch.
+    Returns the search features (2B, C, gs, gs) and the first template's tokens (2B, gt*gt, C) (the score
+    decoder's memory)."""
+    x, n_t = _vit_forward((bb,), t, o, s, ops, drop_path_rate, asym=asym, modal_norms=True, ce=ce,
+                          ce_template_mask=ce_template_mask, ce_keep_rate=ce_keep_rate, ce_forced=ce_forced,
+                          ce_trace=ce_trace)
+    return _search_maps(x, n_t, bb.grid_size_s), x[:, :n_t // 2]
 
 
 def _sine_pos(B, C, H, W, device):
@@ -1911,9 +1909,7 @@ def _cat_fusion_forward(fu, s_v, s_i, ops):
         for i in (1, 2, 3):
             x = getattr(fu, "fusion%d_relu" % i)(getattr(fu, "fusion%d_bn" % i)(getattr(fu, "fusion%d" % i)(x)))
         return x
-    global _BN_TRACKED
-    outer, _BN_TRACKED = _BN_TRACKED, ([] if bn_relu is not None else None)
-    try:
+    with _bn_tracked(ops):
         for i in (1, 2, 3):
             cv, bn = getattr(fu, "fusion%d" % i), getattr(fu, "fusion%d_bn" % i)
             y = conv3x3(x.contiguous(), cv.weight, cv.bias)
@@ -1921,10 +1917,6 @@ def _cat_fusion_forward(fu, s_v, s_i, ops):
                 x = bn_relu(y, bn)
             else:  # cumulative-average norms and SYNC_BN_COLLECTIVE "off": the module on the NCHW map (as the head)
                 x = F.relu(bn(y.permute(0, 3, 1, 2).contiguous())).permute(0, 2, 3, 1).contiguous()
-        if _BN_TRACKED:
-            torch._foreach_add_(_BN_TRACKED, 1)
-    finally:
-        _BN_TRACKED = outer
     return x.permute(0, 3, 1, 2)
 
 
@@ -2097,7 +2089,22 @@ def _hip_bn_ok(bn):
     return type(bn) is torch.nn.BatchNorm2d and bn.momentum is not None
 
 
-_BN_TRACKED = None  # head_forward_nhwc: the num_batches_tracked counters its batch norms advance, added at its end
+_BN_TRACKED = None  # inside _bn_tracked: the num_batches_tracked counters HipOps.bn_relu has to advance
+
+
+@contextlib.contextmanager
+def _bn_tracked(ops):
+    """Gathers the num_batches_tracked advances of the HIP batch norms run inside the block (HipOps.bn_relu appends
+    the counters to the module global _BN_TRACKED) into one multi-tensor add at its normal end; nested blocks keep
+    their own lists.  Ops without bn_relu: nothing is gathered."""
+    global _BN_TRACKED
+    outer, _BN_TRACKED = _BN_TRACKED, ([] if getattr(ops, "bn_relu", None) is not None else None)
+    try:
+        yield
+        if _BN_TRACKED:
+            torch._foreach_add_(_BN_TRACKED, 1)
+    finally:
+        _BN_TRACKED = outer
 
 HEAD_SCORE_FP32 = True  # head_forward_nhwc: the 48 -> 1 conv5 in fp32 (False: bf16 under autocast, as aten's path)
 
@@ -2105,15 +2112,8 @@ HEAD_SCORE_FP32 = True  # head_forward_nhwc: the 48 -> 1 conv5 in fp32 (False: b
 def head_forward_nhwc(hd, x, ops):
     """head_forward with NHWC maps and the 3x3 convolutions on ops.conv3x3 (HIP): _head_forward_nhwc, with the
     HIP batch norms' num_batches_tracked advances gathered into one multi-tensor add at the end."""
-    global _BN_TRACKED
-    outer, _BN_TRACKED = _BN_TRACKED, ([] if getattr(ops, "bn_relu", None) is not None else None)
-    try:
-        out = _head_forward_nhwc(hd, x, ops)
-        if _BN_TRACKED:
-            torch._foreach_add_(_BN_TRACKED, 1)
-    finally:
-        _BN_TRACKED = outer
-    return out
+    with _bn_tracked(ops):
+        return _head_forward_nhwc(hd, x, ops)
 
 
 def _head_forward_nhwc(hd, x, ops):
@@ -2235,13 +2235,7 @@ TOKEN_ROWS = True  # False: NCHW search maps between backbone and fusion (the pr
 def forward_boxes(net, template, online_template, search, ops):
     """MixFormer_RGBT.forward (mixformer.py:366-395) + forward_box_head (:419-432): pred_boxes
     (B, 1, 4) cxcywh.  Stochastic depth at the module's drop_path_rate (as module_forward)."""
-    dpr = getattr(net, "drop_path_rate", DROP_PATH_RATE)
-    s_v, s_i = _backbones_rgbt(net, template, online_template, search, ops, dpr, tokens=_token_rows(ops))
-    with torch.autocast(s_v.device.type, dtype=torch.bfloat16, enabled=s_v.device.type == "cuda"):
-        fused = fusion_forward(net.fusion_vi, s_v, s_i, ops)
-        xyxy = head_forward(net.box_head, fused, ops)
-    x0, y0, x1, y1 = xyxy.float().unbind(-1)
-    return torch.stack([(x0 + x1) / 2, (y0 + y1) / 2, (x1 - x0), (y1 - y0)], -1).view(-1, 1, 4)
+    return module_forward(net, template, online_template, search, ops)[1]
 
 
 def module_forward(net, template, online_template, search, ops, run_score_head=False, gt_bboxes=None,
@@ -2631,8 +2625,7 @@ class TrainStep:
 
 
 class _Wrapped(torch.nn.Module):
-    """nn.Module view of forward_boxes, or for the stacked variants of module_forward's boxes (DDP needs a module
-    whose forward runs the graph)."""
+    """nn.Module view of module_forward's boxes (DDP needs a module whose forward runs the graph)."""
 
     def __init__(self, net, ops):
         super().__init__()
@@ -2640,8 +2633,6 @@ class _Wrapped(torch.nn.Module):
         self.ops = ops
 
     def forward(self, t, o, s, ce_template_mask=None, ce_keep_rate=None):
-        if getattr(self.net, "variant", "rgbt") == "rgbt":
-            return forward_boxes(self.net, t, o, s, self.ops)
         return module_forward(self.net, t, o, s, self.ops, ce_template_mask=ce_template_mask,
                               ce_keep_rate=ce_keep_rate)[1]
 

@@ -385,3 +385,88 @@ def test_ciou_loss_matches_column_form():
         ga, = torch.autograd.grad(la, b1)
         gb, = torch.autograd.grad(lb, b1)
         assert (ga - gb).abs().max().item() <= 1e-6 * gb.abs().max().item()
+
+
+# ----------------------------------------------------------------------------- pinned DropPath draws
+class RecordingOps(TorchPairOps):
+    """TorchPairOps plus the fused one-set residuals (linear_residual / mlp_residual); every residual method appends
+    the keep it was handed to self.keeps."""
+
+    def __init__(self):
+        self.keeps = []
+
+    def _add(self, x, y, keep):
+        self.keeps.append(keep)
+        y = y.view(x.shape)
+        return x + (y if keep is None else y * keep.view(-1, 1, 1))
+
+    def linear_residual(self, x, a, weight, bias, keep):
+        return self._add(x, F.linear(a, weight, bias), keep)
+
+    def mlp_residual(self, x, xn, w1, b1, w2, b2, keep):
+        return self._add(x, F.linear(F.gelu(F.linear(xn, w1, b1)), w2, b2), keep)
+
+    def linear_residual2(self, x, a, w0, b0, w1, b1, keep):
+        return self._add(x, TorchPairOps.linear2(a, w0, b0, w1, b1), keep)
+
+    def mlp_residual2(self, x, xn, p0, p1, keep):
+        h = xn.shape[0] // 2
+        return self._add(x, torch.cat([F.linear(F.gelu(F.linear(u, p[0], p[1])), p[2], p[3])
+                                       for u, p in ((xn[:h], p0), (xn[h:], p1))], 0), keep)
+
+
+def _per_branch_keeps(rows, depth, rate):
+    """The one-set recipe: per live residual branch, attention then MLP in block order, one draw over the rows."""
+    out = []
+    for li in range(depth):
+        p = rate * li / max(depth - 1, 1)
+        for _ in range(2):
+            out.append(torch.empty(rows).bernoulli_(1.0 - p).div_(1.0 - p) if p > 0.0 else None)
+    return out
+
+
+@pytest.mark.parametrize("form", ["single", "pair", "shared", "asym"])
+def test_backbone_drop_path_draws_are_pinned(form):
+    """The DropPath scales each public backbone wrapper hands its residual ops (train() mode, rate 0.1, B = 2), against
+    the draws regenerated from the same seed by the wrapper's documented recipe: count, order, shapes, probabilities
+    and the None entries of the rate-0 first block, exactly."""
+    import mmt_amd.model as M
+    from mmt_amd import train
+    torch.set_num_threads(8)
+    rate, seed, B = 0.1, 11, 2
+    torch.manual_seed(0)
+    builder = {"single": "rgbt", "pair": "rgbt", "shared": "shared", "asym": "asym"}[form]
+    net = getattr(M, BUILDERS[builder])(M.hot_path_cfg(search=SEARCH, template=TEMPLATE), train=False).train()
+    t, o, s, _ = _batch(B, 2)
+    ops = RecordingOps()
+    torch.manual_seed(seed)
+    with torch.no_grad():
+        if form == "single":
+            depth = len(net.backbone_v.blocks)
+            train.backbone_forward(net.backbone_v, t[0], o[0], s[0], ops, rate)
+        elif form == "pair":
+            depth = len(net.backbone_v.blocks)
+            train.backbone_forward_pair(net.backbone_v, net.backbone_i, t, o, s, ops, rate)
+        else:
+            depth = len(net.backbone.blocks)
+            train.backbone_forward_stacked(net.backbone, torch.cat(t, 0), torch.cat(o, 0), torch.cat(s, 0), ops,
+                                           asym=form == "asym", drop_path_rate=rate)
+    torch.manual_seed(seed)
+    if form == "pair":  # one draw over [live branches][2B] before the loop
+        ps = [rate * (i // 2) / max(depth - 1, 1) for i in range(2 * depth)]
+        live = [i for i, p in enumerate(ps) if p > 0.0]
+        assert len(live) == 2 * depth - 2 == 22
+        q = torch.tensor([[1.0 - ps[i]] for i in live], dtype=torch.float32)
+        k = torch.empty(len(live), 2 * B).bernoulli_(q.expand(-1, 2 * B)).div_(q)
+        want = [None] * (2 * depth)
+        for j, i in enumerate(live):
+            want[i] = k[j]
+    else:
+        want = _per_branch_keeps(B if form == "single" else 2 * B, depth, rate)
+    got = ops.keeps
+    assert len(got) == len(want) == 2 * depth
+    assert got[0] is None and got[1] is None
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert (g is None) == (w is None), i
+        if w is not None:
+            assert g.dtype == w.dtype and g.shape == w.shape and torch.equal(g, w), i
