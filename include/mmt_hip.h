@@ -28,11 +28,13 @@
  *       parallel conv chains head.py:159-197, the encoder's value / offset Linears)
  *   mmt_mam_attention           Attention.forward MAM softmax(QK^T)V, mixformer.py:52-78 /
  *       asymmetric_shared.py:55-104
+ *   mmt_mam_attention_tl        the same with a count of valid template rows per sequence (online template memory)
  *   mmt_mam_attention_bwd       its autograd (training step, train_script_mixformer*.py)
  *   mmt_transpose_bf16          operand transposes of the Linear backward (nn.Linear autograd)
  *   mmt_adamw_step              gradient clipping + AdamW over every parameter (torch.optim.AdamW)
  *   mmt_layernorm / mmt_groupnorm  nn.LayerNorm / nn.GroupNorm on the hot path
  *   mmt_patch_im2col            PatchEmbed conv input staging, mixformer.py:29-34
+ *   mmt_patch_im2col_mem        the same for 1 + K templates per sequence (mixformer_vit_online.py's online_size)
  *   mmt_msda_bimodal            MSDeformAttn_Bimodal.forward middle part (offset/weight softmax,
  *       sampling locations, MSDA gather), ms_deform_attn_bimodal.py:97-128
  *   mmt_corner_softargmax       conv5 + pyramid adds + soft_argmax + box_xyxy_to_cxcywh,
@@ -277,6 +279,18 @@ typedef struct {
 
 int mmt_mam_attention(const mmt_attn_params* p, int dtype, void* stream);
 
+/* The same with a count of valid template rows per sequence (the online template memory, whose slots fill
+ * over a sequence's first updates): tmpl_len_dev is int32[S] in device memory, read by the kernels only, so
+ * one captured launch serves every value.  With tl = tmpl_len_dev[s], sequence s behaves as if its template
+ * rows were [0, tl): template queries [0, tl) attend keys [0, tl); template queries [tl, n_t) are not computed
+ * and their out rows are not written; search queries attend [0, tl) and [n_t, ntok), or with asym == 1
+ * [0, tl[sV]) of sV, [0, tl[sI]) of sI and their own search rows.  Rows stay where they are (tok_pitch,
+ * out_pitch, out_q0 and q_part keep their meaning), and the key walk is that of a launch with n_t = tl.  A tl
+ * outside 1..n_t (for a search query with asym == 1: of sV or sI too) skips the sequence: nothing is stored.
+ * impl 0 / 4 / 8 / 21 / 22 (fp32: its two kernels); MMT_EBADARG for lse != NULL and for impl 17 / 29.
+ * tmpl_len_dev == NULL is mmt_mam_attention. */
+int mmt_mam_attention_tl(const mmt_attn_params* p, const int32_t* tmpl_len_dev, int dtype, void* stream);
+
 /* MAM attention backward (training; bf16), of both key layouts of the forward.  qkv / out as in the
  * forward (q NOT pre-scaled: pass the natural `scale`), dout = dL/dout [S][ntok][C], lse from the
  * forward with the same qkv, scale and asym; delta: [S][H][ntok] fp32 workspace; dqkv:
@@ -369,6 +383,13 @@ int mmt_scale_rows_cast(const float* in, const float* scale, int64_t rows_per, v
 int mmt_patch_im2col(const float* img_t0, const float* img_t1, const float* img_o0, const float* img_o1,
                      const float* img_s0, const float* img_s1, void* out, int Bm, int ht, int hs, int patch,
                      int dtype, void* stream);
+
+/* The same for K online templates per sequence (mixformer_vit_online.py's online_size): img_o[m] is one
+ * [Bm][K][3][ht][ht] tensor and the row block is [tmpl | online 0 | .. | online K-1 | search],
+ * (1 + K) (ht/patch)^2 + (hs/patch)^2 rows.  K = 1 writes mmt_patch_im2col's rows. */
+int mmt_patch_im2col_mem(const float* img_t0, const float* img_t1, const float* img_o0, const float* img_o1,
+                         const float* img_s0, const float* img_s1, void* out, int Bm, int K, int ht, int hs,
+                         int patch, int dtype, void* stream);
 
 /* ---------------------------------------------------------------- deformable attention
  * Reference-op replacement: value (N,S,M,D), spatial_shapes (L,2) int64, level_start (L) int64,

@@ -21,6 +21,9 @@
 //            wave per SIMD; 28: ping-pong), each bit-identical to 22 and measured slower.  DESIGN.md §8
 //            and profiles/ keep the numbers, git history keeps the code; the dispatcher rejects them.
 // Which keys a query block sees, and where they live, is stated once: MamBlock in attn_common.hpp.
+// mmt_mam_attention_tl launches the same kernels with a count of valid template rows per sequence, read from
+// device memory (the online template memory): MamBlock's TL form, instantiations of their own
+// (fp32, impl 4 / 8 / 21 / 22), so the launches without lengths keep their generated code.
 // Scores are computed transposed (S^T = K Q^T) so that each lane owns one query column: the softmax
 // statistics need no cross-lane reduction and the exponentiated scores are already laid out as the B
 // operand of O^T = V^T P^T (no LDS round trip for P).  V^T fragments come from ds_read_b64_tr_b16 on
@@ -46,8 +49,11 @@ struct AttnCfg {
 };
 
 // QT = 16-query MFMA tiles per wave (1: 4 waves x 16 queries, for small grids; 2: 2 waves x 32).
-template <typename T, int QT>
-__global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_params p) {
+// Every kernel below ends its parameters with TLEN... tlen: empty (mmt_mam_attention), or the per-sequence
+// template lengths of mmt_mam_attention_tl (MamBlock<.., TL = true> in attn_common.hpp).
+template <typename T, int QT, typename... TLEN>
+__global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_params p, TLEN... tlen) {
+    constexpr bool TL = attn_has_len<TLEN...>;
     constexpr int NTH = 256 / QT;
     using Cfg = AttnCfg<T>;
     constexpr int KCH = Cfg::KCH, QCH = Cfg::QCH, VROW = Cfg::VROW;
@@ -56,7 +62,10 @@ __global__ __launch_bounds__(256 / QT) void mam_attention_kernel(const mmt_attn_
 
     int bx, h, s;
     attn_block_ids<false>(bx, h, s);
-    const MamBlock<T, 64> blk(p, bx, s);
+    const MamBlock<T, 64, TL> blk(p, bx, s, tlen...);
+    if constexpr (TL) {
+        if (!blk.live) return;
+    }
     const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
     const int64_t pitch = blk.pitch;
 
@@ -284,9 +293,10 @@ constexpr int ATILE = 2 * KB * 128; // bytes of one slot: K image then V image
 // NS = ring slots (tiles held).  (KG 3 with 9 slots, the whole 528-key stream issued in the prologue
 // and three full rounds, measured no faster: 9.64 vs 9.49 us at B = 1 -- the per-CU fill of the
 // 136 KiB of K / V, not the DMA rounds, bounds this kernel.)
-template <typename T, int KG, int NS = ANS>
+template <typename T, int KG, int NS, typename... TLEN>
 __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG))) void mam_attention_glds_kernel(
-    const mmt_attn_params p) {
+    const mmt_attn_params p, TLEN... tlen) {
+    constexpr bool TL = attn_has_len<TLEN...>;
     constexpr int NWV = 4 * KG;  // waves; a tile's 16 K/V pieces go to waves piece % NWV
     constexpr int R = NS / KG;   // rounds (KG tiles each) held by the ring
     static_assert(R >= 2 && NWV <= 16 && NWV >= 8 && R * KG == NS, "ring geometry");
@@ -298,7 +308,10 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
     int bx, h, s;
     attn_block_ids<false>(bx, h, s);  // (grouping a (sequence, head)'s query blocks on one XCD measured
                                       // slower at batch 1: 8.94 vs 8.47 us in the frame)
-    const MamBlock<T, 64> blk(p, bx, s);
+    const MamBlock<T, 64, TL> blk(p, bx, s, tlen...);
+    if constexpr (TL) {
+        if (!blk.live) return;
+    }
     const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
     const int64_t pitch = blk.pitch;
 
@@ -518,15 +531,19 @@ __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(KG, KG
 #endif
 constexpr float FA_THR = 8.f;
 
-template <typename T, int FNS, int OCC>  // storage type, ring depth, workgroups per CU
+template <typename T, int FNS, int OCC, typename... TLEN>  // storage type, ring depth, workgroups per CU
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void mam_attention_fa_kernel(
-    const mmt_attn_params p) {
+    const mmt_attn_params p, TLEN... tlen) {
+    constexpr bool TL = attn_has_len<TLEN...>;
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE + FQ * 128];
     char* qimg = lds + FNS * FTILE;
 
     int bx, h, s;
     attn_block_ids<false>(bx, h, s);
-    const MamBlock<T, FQ> blk(p, bx, s);
+    const MamBlock<T, FQ, TL> blk(p, bx, s, tlen...);
+    if constexpr (TL) {
+        if (!blk.live) return;
+    }
     const int ntok = p.ntok, C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
     const int64_t pitch = blk.pitch;
 
@@ -750,15 +767,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // VALU.  B = 32: 78.9 vs 83.8 us, asym 88.5 vs 93.2; B = 8: 27.2 vs 29.8 (same run, bit-identical
 // output).  Measured and dropped: sched_group_barrier interleave hints (79.3), the block-1 PV moved
 // past the next tile's barrier (79.6), 2 workgroups per CU (85.3).
-template <int FNS, int OCC, bool SUM_MFMA, bool PIPE = false>
+template <int FNS, int OCC, bool SUM_MFMA, bool PIPE, typename... TLEN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void mam_attention_lz_kernel(
-    const mmt_attn_params p) {
+    const mmt_attn_params p, TLEN... tlen) {
+    constexpr bool TL = attn_has_len<TLEN...>;
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE];
 
-    MamBlock<bf16_t, FQ> blk(p);
+    MamBlock<bf16_t, FQ, TL> blk(p);
     int bx, h, s;
     attn_block_ids<true>(bx, h, s);
-    blk.place(p, bx, s);
+    blk.place(p, bx, s, tlen...);
+    if constexpr (TL) {
+        if (!blk.live) return;
+    }
     const int ntok = p.ntok, C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
     const int64_t pitch = blk.pitch;
 
@@ -1063,9 +1084,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // Every LDS-DMA it issues has landed when it returns (the last tile's wait is vmcnt(0)); its output
 // stores may still be in flight.  (A persistent form that looped over these items in a longest-first
 // static order measured no faster: profiles/r03_attn_persistent_ab.jsonl.)
-template <int FNS, bool SPLIT = true, bool PIPE2 = true>
-MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, const int h, const int s) {
-    const MamBlock<bf16_t, FQ> blk(p, bx, s);
+template <int FNS, bool SPLIT = true, bool PIPE2 = true, typename... TLEN>
+MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, const int h, const int s, TLEN... tlen) {
+    constexpr bool TL = attn_has_len<TLEN...>;
+    const MamBlock<bf16_t, FQ, TL> blk(p, bx, s, tlen...);
+    if constexpr (TL) {
+        if (!blk.live) return;
+    }
     const int C = p.C, q0 = blk.q0, qend = blk.qend, Lk = blk.Lk;
     const int64_t pitch = blk.pitch;
 
@@ -1362,13 +1387,13 @@ MMT_DEV void mam_lz2_item(const mmt_attn_params& p, char* lds, const int bx, con
     }
 }
 
-template <int FNS>
+template <int FNS, typename... TLEN>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void mam_attention_lz2_kernel(
-    const mmt_attn_params p) {
+    const mmt_attn_params p, TLEN... tlen) {
     __shared__ __attribute__((aligned(1024))) char lds[FNS * FTILE];
     int bx, h, s;
     attn_block_ids<true>(bx, h, s);
-    mam_lz2_item<FNS>(p, lds, bx, h, s);
+    mam_lz2_item<FNS, true, true>(p, lds, bx, h, s, tlen...);
 }
 
 }  // namespace
@@ -1378,7 +1403,9 @@ int mmt_attn_launch_ps(const mmt_attn_params& p, hipStream_t st);  // attention_
 namespace {
 
 template <typename T>
-int launch_attn(const mmt_attn_params& p, hipStream_t st) {
+int launch_attn(const mmt_attn_params& p, hipStream_t st, const int32_t* tlen = nullptr) {
+    // tlen (mmt_mam_attention_tl): the inference kernels impl 0 can pick; no log-sum-exp, no impl 17, no persistent form
+    if (tlen && (p.lse || p.impl == 17 || p.impl == 29)) return MMT_EBADARG;
     // impl: 0 = the library's choice by dtype and grid size; forced (A/B and tests): 4 = latency kernel,
     // 8 = running-maximum throughput kernel, 17 / 21 / 22 = range-checked exponent kernels (22 = 64
     // queries per wave), 29 = the persistent form of 22.  23-28 were A/B-only experiments, since removed
@@ -1428,19 +1455,30 @@ int launch_attn(const mmt_attn_params& p, hipStream_t st) {
             else if (p.lse || wg >= MMT_ATTN_FA_MIN_WG) impl = 8;
             else impl = 4;
         }
-        if (impl == 17) hipLaunchKernelGGL((mam_attention_lz_kernel<3, 3, true>), fgrid, dim3(256), 0, st, p);
-        else if (impl == 21) hipLaunchKernelGGL((mam_attention_lz_kernel<3, 3, true, true>), fgrid, dim3(256), 0, st, p);
-        else if (impl == 22) hipLaunchKernelGGL((mam_attention_lz2_kernel<2>), fgrid, dim3(128), 0, st, p);
+        // plain: the kernel without lengths; tl: the same kernel with the lengths as its last argument
+        using TLP = const int32_t*;
+        auto launch = [&](auto plain, auto tl, dim3 g, dim3 b) {
+            if (tlen) hipLaunchKernelGGL(tl, g, b, 0, st, p, tlen);
+            else hipLaunchKernelGGL(plain, g, b, 0, st, p);
+        };
+        if (impl == 17) hipLaunchKernelGGL((mam_attention_lz_kernel<3, 3, true, false>), fgrid, dim3(256), 0, st, p);
+        else if (impl == 21) launch(mam_attention_lz_kernel<3, 3, true, true>, mam_attention_lz_kernel<3, 3, true, true, TLP>, fgrid, dim3(256));
+        else if (impl == 22) launch(mam_attention_lz2_kernel<2>, mam_attention_lz2_kernel<2, TLP>, fgrid, dim3(128));
         else if (impl == 29) {  // persistent kernel: bf16 only, its own shape check
             if (!bf) return MMT_EBADARG;
             const int rc = mmt_attn_launch_ps(p, st);
             if (rc) return rc;
         }
-        else if (impl == 8 || p.lse) hipLaunchKernelGGL((mam_attention_fa_kernel<T, 2, 3>), fgrid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((mam_attention_glds_kernel<T, 4>), grid, dim3(1024), 0, st, p);
+        else if (impl == 8 || p.lse) launch(mam_attention_fa_kernel<T, 2, 3>, mam_attention_fa_kernel<T, 2, 3, TLP>, fgrid, dim3(256));
+        else launch(mam_attention_glds_kernel<T, 4, ANS>, mam_attention_glds_kernel<T, 4, ANS, TLP>, grid, dim3(1024));
     } else {  // fp32 (parity path); small grids: 4 waves x 16 queries to occupy more SIMDs
-        if ((int64_t)nqb * p.H * p.S < 1024) hipLaunchKernelGGL((mam_attention_kernel<T, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((mam_attention_kernel<T, 2>), grid, dim3(128), 0, st, p);
+        using TLP = const int32_t*;
+        auto launch = [&](auto plain, auto tl, dim3 b) {
+            if (tlen) hipLaunchKernelGGL(tl, grid, b, 0, st, p, tlen);
+            else hipLaunchKernelGGL(plain, grid, b, 0, st, p);
+        };
+        if ((int64_t)nqb * p.H * p.S < 1024) launch(mam_attention_kernel<T, 1>, mam_attention_kernel<T, 1, TLP>, dim3(256));
+        else launch(mam_attention_kernel<T, 2>, mam_attention_kernel<T, 2, TLP>, dim3(128));
     }
     return launch_status();
 }
@@ -1452,5 +1490,13 @@ extern "C" int mmt_mam_attention(const mmt_attn_params* p, int dtype, void* stre
     if (dtype == MMT_BF16) return launch_attn<bf16_t>(*p, (hipStream_t)stream);
     if (dtype == MMT_F16) return launch_attn<f16_t>(*p, (hipStream_t)stream);
     if (dtype == MMT_F32) return launch_attn<float>(*p, (hipStream_t)stream);
+    return MMT_EBADARG;
+}
+
+extern "C" int mmt_mam_attention_tl(const mmt_attn_params* p, const int32_t* tmpl_len_dev, int dtype, void* stream) {
+    if (!p) return MMT_EBADARG;
+    if (dtype == MMT_BF16) return launch_attn<bf16_t>(*p, (hipStream_t)stream, tmpl_len_dev);
+    if (dtype == MMT_F16) return launch_attn<f16_t>(*p, (hipStream_t)stream, tmpl_len_dev);
+    if (dtype == MMT_F32) return launch_attn<float>(*p, (hipStream_t)stream, tmpl_len_dev);
     return MMT_EBADARG;
 }

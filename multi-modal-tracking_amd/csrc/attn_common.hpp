@@ -119,15 +119,26 @@ MMT_DEV int attn_vswz(int row) { return (row & 6) ^ ((row & 2) << 1); }
 // template of the TIR sequence sI = sV + Bm, and [2 n_t, ntok + n_t) the own search tokens n_t .. ntok - 1.
 // Row pointers are to the row's start: callers add the k / v and head offsets.
 // (A base of MamBlock, not part of it: merged into one struct the kernels compile to different code.)
-template <typename T>
+// TL = true (mmt_mam_attention_tl): every sequence has its own count of valid template rows, tl <= n_t.
+// n_t is then the length of the block's own sequence and nV / nI those of sV / sI, the stream is that of a
+// launch with those lengths, and the rows stay where they are: search rows start at row np (the launch's
+// n_t).  TL = false keeps the code below as it was, statement for statement.
+template <typename T, bool TL = false>
 struct MamKeys {
     const T* qkv;
     int64_t pitch, rs;
     int n_t, s, sV, sI;
     bool cross;
+    int np, nV, nI;  // TL only
     MMT_DEV const T* key_row(int kk) const {
         int seq = s, row = kk;
-        if (cross) {
+        if constexpr (TL) {
+            if (cross) {
+                if (kk < nV) seq = sV;
+                else if (kk < nV + nI) { seq = sI; row = kk - nV; }
+                else row = kk - nV - nI + np;
+            } else if (kk >= n_t) row = kk - n_t + np;
+        } else if (cross) {
             if (kk < n_t) seq = sV;
             else if (kk < 2 * n_t) { seq = sI; row = kk - n_t; }
             else row = kk - n_t;
@@ -144,11 +155,21 @@ struct MamKeys {
 // block.  Template queries see the sequence's own template keys (Lk = n_t); search queries see every own
 // token (Lk = ntok) or, cross-modal (p.asym), the stream of MamKeys (Lk = ntok + n_t).  Keys are consumed
 // in nkt() tiles of KB; the last may be short.
-template <typename T, int QB>
-struct MamBlock : MamKeys<T> {
+// TL = true: place() takes the lengths int32[S]; the grid and the block numbering are the launch's (n_t
+// rows of template blocks), a block is live when its sequence's lengths are in 1..n_t and, for a template
+// block, when it starts below tl.  The kernels return on a dead block before any DMA, barrier or store; the
+// decision is the same for every thread of the workgroup.  The kernels take the lengths as a parameter pack
+// (TLEN...: empty, or one const int32_t*), so that the launches without lengths keep their kernel arguments
+// and their code; attn_has_len names which form a pack selects.
+template <typename... TLEN>
+constexpr bool attn_has_len = sizeof...(TLEN) == 1;
+template <typename T, int QB, bool TL = false>
+struct MamBlock : MamKeys<T, TL> {
     int ntok, nqb_t, q0, qend, Lk;
     bool tmpl;
+    bool live;  // TL only
     MMT_DEV MamBlock(const mmt_attn_params& p, int bx, int s) : MamBlock(p) { place(p, bx, s); }
+    MMT_DEV MamBlock(const mmt_attn_params& p, int bx, int s, const int32_t* tlen) : MamBlock(p) { place(p, bx, s, tlen); }
     // The same in two steps, the launch-only part first and the block's place after the kernel has read its
     // block ids (impl 17 / 21 is written in that order and its generated code depends on it); the block
     // is valid after place().
@@ -172,8 +193,24 @@ struct MamBlock : MamKeys<T> {
         this->sV = s % p.Bm;
         this->sI = this->sV + p.Bm;
     }
+    MMT_DEV void place(const mmt_attn_params& p, int bx, int s, const int32_t* tlen) {
+        static_assert(TL, "lengths belong to the TL form");
+        place(p, bx, s);
+        const int np = p.n_t, tl = tlen[s], tV = p.asym ? tlen[this->sV] : tl, tI = p.asym ? tlen[this->sI] : tl;
+        this->np = np;
+        this->n_t = tl;
+        this->nV = tV;
+        this->nI = tI;
+        live = tl >= 1 && tl <= np && (tmpl ? q0 < tl : (tV >= 1 && tV <= np && tI >= 1 && tI <= np));
+        if (tmpl) qend = tl;
+        Lk = tmpl ? tl : ntok - np + (p.asym ? tV + tI : tl);
+    }
     MMT_DEV int nkt() const { return (Lk + KB - 1) / KB; }
-    MMT_DEV bool aligned() const { return this->n_t % KB == 0; }  // no full key tile straddles two key segments
+    // no full key tile straddles two key segments
+    MMT_DEV bool aligned() const {
+        if constexpr (TL) return (this->n_t | this->nV | this->nI) % KB == 0;
+        else return this->n_t % KB == 0;
+    }
     // query q, clamped to the block's last query (rows past it are staged and computed, never stored)
     MMT_DEV const T* q_row(int q) const { return this->qkv + ((int64_t)this->s * this->pitch + min(q, qend - 1)) * this->rs; }
 };
@@ -182,8 +219,8 @@ struct MamBlock : MamKeys<T> {
 // (rows past the block's end re-read its last query), 128 B per row at head h, chunk c of row r stored at
 // c ^ (r & 7); this lane moves chunk pcol of row prow.  (One piece per call: the piece loops stay in the
 // kernels, where moving them into a helper changes the generated code.)
-template <typename T, int QB>
-MMT_DEV void attn_issue_q(const MamBlock<T, QB>& blk, int h, char* qimg, int piece, int prow, int pcol) {
+template <typename T, int QB, bool TL>
+MMT_DEV void attn_issue_q(const MamBlock<T, QB, TL>& blk, int h, char* qimg, int piece, int prow, int pcol) {
     const int r = piece * 8 + prow;
     const T* src = blk.q_row(blk.q0 + r) + h * D;
     attn_glds16(src + ((pcol ^ prow) * 8), qimg + piece * 1024);

@@ -9,6 +9,7 @@
 //   mmt_groupnorm_bwd  its backward for the training step (dx, dgamma / dbeta; channels-last)
 //   mmt_add_cast     src + pos -> bf16 query staging (ms_deform_attn_bimodal.py:93-95)
 //   mmt_patch_im2col PatchEmbed input staging for the patch GEMM (mixformer.py:29-34, :237-247)
+//   mmt_patch_im2col_mem  the same for a template and K online templates per sequence
 #include "common.hpp"
 
 namespace {
@@ -483,6 +484,42 @@ __global__ void patch_im2col_kernel(const float* t0, const float* t1, const floa
     }
 }
 
+// The same for a memory of K online templates: rows [tmpl | online 0 | .. | online K-1 | search], the online
+// images of a modality as one [Bm][K][3][ht][ht] tensor.  K = 1 writes patch_im2col_kernel's rows.
+template <typename T>
+__global__ void patch_im2col_mem_kernel(const float* t0, const float* t1, const float* o0, const float* o1,
+                                        const float* s0, const float* s1, T* out, int Bm, int K, int ht, int hs, int P,
+                                        int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int gt = ht / P, gs = hs / P;
+    const int nt = gt * gt, ntok = (1 + K) * nt + gs * gs;
+    const int ky = idx % P;
+    const int c = (idx / P) % 3;
+    const int64_t row = idx / (3 * P);
+    const int tok = row % ntok;
+    const int64_t seq = row / ntok;
+    const int m = (int)(seq / Bm), b = (int)(seq % Bm);
+    const float* img;  // the (b, 0) plane of the token's image
+    int hw, g, t;
+    if (tok < nt) { img = (m ? t1 : t0) + (int64_t)b * 3 * ht * ht; hw = ht; g = gt; t = tok; }
+    else if (tok < (1 + K) * nt) {
+        const int k = tok / nt - 1;
+        img = (m ? o1 : o0) + ((int64_t)b * K + k) * 3 * ht * ht; hw = ht; g = gt; t = tok - (1 + k) * nt;
+    }
+    else { img = (m ? s1 : s0) + (int64_t)b * 3 * hs * hs; hw = hs; g = gs; t = tok - (1 + K) * nt; }
+    const int py = t / g, px = t % g;
+    const float* src = img + ((int64_t)c * hw + (py * P + ky)) * hw + px * P;
+    T* dst = out + row * (3 * P * P) + (c * P + ky) * P;
+    for (int kx = 0; kx < P; kx += 4) {
+        const float4 v = *(const float4*)(src + kx);
+        dst[kx + 0] = from_f<T>(v.x);
+        dst[kx + 1] = from_f<T>(v.y);
+        dst[kx + 2] = from_f<T>(v.z);
+        dst[kx + 3] = from_f<T>(v.w);
+    }
+}
+
 }  // namespace
 
 extern "C" int mmt_layernorm(const float* in, const float* add, int64_t add_rows, float* out_f32, void* out_t,
@@ -643,6 +680,31 @@ extern "C" int mmt_patch_im2col(const float* img_t0, const float* img_t1, const 
     else if (dtype == MMT_F32)
         hipLaunchKernelGGL((patch_im2col_kernel<float>), grid, dim3(256), 0, st, img_t0, img_t1, img_o0, img_o1,
                            img_s0, img_s1, (float*)out, Bm, ht, hs, patch, total);
+    else return MMT_EBADARG;
+    return launch_status();
+}
+
+extern "C" int mmt_patch_im2col_mem(const float* img_t0, const float* img_t1, const float* img_o0, const float* img_o1,
+                                    const float* img_s0, const float* img_s1, void* out, int Bm, int K, int ht, int hs,
+                                    int patch, int dtype, void* stream) {
+    const int nmod = (!img_t1 && !img_o1 && !img_s1) ? 1 : 2;
+    if (!img_t0 || !img_o0 || !img_s0 || !out || Bm <= 0 || K <= 0) return MMT_EBADARG;
+    if (nmod == 2 && (!img_t1 || !img_o1 || !img_s1)) return MMT_EBADARG;
+    if (patch <= 0 || patch % 4 || ht % patch || hs % patch) return MMT_EBADARG;
+    const int gt = ht / patch, gs = hs / patch;
+    const int64_t rows = (int64_t)nmod * Bm * ((int64_t)(1 + K) * gt * gt + gs * gs);
+    const int64_t total = rows * 3 * patch;
+    dim3 grid((unsigned)((total + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMT_BF16)
+        hipLaunchKernelGGL((patch_im2col_mem_kernel<bf16_t>), grid, dim3(256), 0, st, img_t0, img_t1, img_o0, img_o1,
+                           img_s0, img_s1, (bf16_t*)out, Bm, K, ht, hs, patch, total);
+    else if (dtype == MMT_F16)
+        hipLaunchKernelGGL((patch_im2col_mem_kernel<f16_t>), grid, dim3(256), 0, st, img_t0, img_t1, img_o0, img_o1,
+                           img_s0, img_s1, (f16_t*)out, Bm, K, ht, hs, patch, total);
+    else if (dtype == MMT_F32)
+        hipLaunchKernelGGL((patch_im2col_mem_kernel<float>), grid, dim3(256), 0, st, img_t0, img_t1, img_o0, img_o1,
+                           img_s0, img_s1, (float*)out, Bm, K, ht, hs, patch, total);
     else return MMT_EBADARG;
     return launch_status();
 }

@@ -14,7 +14,7 @@ Each module also has `get_batch_tracker_class()`: the same tracker for `slots` s
 """
 import torch
 
-from mmt_amd.tracking import RGBTBatchTrackerCore, RGBTTrackerCore
+from mmt_amd.tracking import RGBTBatchTrackerCore, RGBTTrackerCore, check_online_memory
 
 try:  # the reference's BaseTracker (with its visdom helpers) when its lib/ is overlaid
     from lib.test.tracker.basetracker import BaseTracker
@@ -38,10 +38,19 @@ def _update_intervals(cfg, dataset_name):
 KV_CACHE_DEFAULT = False
 
 
+def _online_memory(params, online_score):
+    """params.online_size (upstream mixformer_vit_online.py's online_size / TEST.ONLINE_SIZES; default 1, the RGB-T
+    fork's one online template) and params.max_score_decay (default 1.0), as the cores' keywords.  Checked before
+    the network is built: the plain trackers refuse online_size > 1 (ValueError)."""
+    K, decay = check_online_memory(getattr(params, "online_size", 1), getattr(params, "max_score_decay", 1.0), online_score)
+    return {"online_size": K, "max_score_decay": decay}
+
+
 def make_tracker_class(builder, multimodal, online_score=False, kv_cache=KV_CACHE_DEFAULT):
     class MixFormer(BaseTracker):
         def __init__(self, params, dataset_name):
             super().__init__(params)
+            memory = _online_memory(params, online_score)
             network = builder(params.cfg, train=False)
             if getattr(params, "checkpoint", None):
                 ck = torch.load(params.checkpoint, map_location="cpu", weights_only=True)
@@ -49,12 +58,14 @@ def make_tracker_class(builder, multimodal, online_score=False, kv_cache=KV_CACH
             self.cfg = params.cfg
             self.network = network.cuda()
             self.network.eval()
+            if memory["online_size"] > 1:
+                self.network.set_online_size(memory["online_size"])
             self.save_all_boxes = getattr(params, "save_all_boxes", False)
             self.update_intervals = _update_intervals(self.cfg, dataset_name)
             self.core = RGBTTrackerCore(self.network, params.template_factor, params.template_size,
                                         params.search_factor, params.search_size, self.update_intervals,
                                         multimodal=multimodal, online_score=online_score,
-                                        kv_cache=getattr(params, "kv_cache", kv_cache))
+                                        kv_cache=getattr(params, "kv_cache", kv_cache), **memory)
             self.state = None
             self.frame_id = 0
 
@@ -103,6 +114,9 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
             if getattr(params, "save_all_boxes", False):
                 raise NotImplementedError("save_all_boxes is not supported by the batched tracker")
             self.params = params
+            memory = _online_memory(params, online_score)
+            if memory["online_size"] > 1 and getattr(params, "pack_slots", None):
+                raise ValueError("pack_slots is not implemented for online_size > 1")
             network = builder(params.cfg, train=False)
             if getattr(params, "checkpoint", None):
                 ck = torch.load(params.checkpoint, map_location="cpu", weights_only=True)
@@ -110,6 +124,8 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
             self.cfg = params.cfg
             self.network = network.cuda()
             self.network.eval()
+            if memory["online_size"] > 1:
+                self.network.set_online_size(memory["online_size"])
             self.update_intervals = _update_intervals(self.cfg, dataset_name)
             self.slots = int(slots)
             self.core = RGBTBatchTrackerCore(self.network, params.template_factor, params.template_size,
@@ -118,7 +134,7 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
                                              kv_cache=getattr(params, "kv_cache", False), slots=self.slots,
                                              slot_cache=getattr(params, "slot_cache", False),
                                              refresh_slots=getattr(params, "refresh_slots", None),
-                                             pack=getattr(params, "pack_slots", None))
+                                             pack=getattr(params, "pack_slots", None), **memory)
 
         def initialize(self, slot, image, info: dict):
             """image: [image_v, image_i]; info["init_bbox"]: (bbox_v, bbox_i), the RGB box is used."""

@@ -89,6 +89,7 @@ _PROTOS = {
     "mmt_gemm_multi": [ctypes.POINTER(GemmParams), i32, i32, vp],
     "mmt_gemm_select": [ctypes.POINTER(GemmParams), i32, i32, ctypes.POINTER(GemmChoice)],
     "mmt_mam_attention": [ctypes.POINTER(AttnParams), i32, vp],
+    "mmt_mam_attention_tl": [ctypes.POINTER(AttnParams), vp, i32, vp],
     "mmt_mam_attention_bwd": [ctypes.POINTER(AttnBwdParams), i32, vp],
     "mmt_transpose_bf16": [vp, vp, i32, i32, i64, i64, i32, i64, i64, i32, vp],
     "mmt_im2col3x3_bf16": [vp, vp, i32, i32, i32, i32, vp],
@@ -107,6 +108,7 @@ _PROTOS = {
     "mmt_add_cast": [vp, vp, i64, vp, vp, i64, i32, vp],
     "mmt_scale_rows_cast": [vp, vp, i64, vp, i64, i64, i32, vp],
     "mmt_patch_im2col": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "mmt_patch_im2col_mem": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "mmt_ms_deform_attn_forward": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "mmt_ms_deform_attn_backward": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "mmt_ms_deform_attn_backward_impl": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,

@@ -331,6 +331,10 @@ class _HipTracker(nn.Module):
     variant = None
     train_ops = None  # None = mmt_amd.train.HipOps (the product); tests on CPU inject a stand-in
     drop_path_rate = 0.1  # the backbone's stochastic depth in training (mixformer.py:311, :324)
+    # online templates per sequence (mixformer_vit_online.py's ONLINE_SIZES; set_online_size).  K > 1: online_template
+    # is (B, K, 3, h, h) per modality and forward / set_online / forward_test take online_count=(B,) in 1..K,
+    # the filled slots of each sequence (inference only)
+    online_size = 1
 
     def __init__(self, head_type="CORNER_UP"):
         super().__init__()
@@ -356,20 +360,41 @@ class _HipTracker(nn.Module):
         self._online_batch = None
         return super()._apply(fn, *args, **kwargs)
 
+    def set_online_size(self, online_size):
+        """K online templates per sequence (1: the one online template of the RGB-T fork)."""
+        if int(online_size) != online_size or online_size < 1:
+            raise ValueError("online_size must be an integer >= 1, got %r" % (online_size,))
+        if online_size > 1 and self.variant in ("asym_ce", "rgb"):
+            raise NotImplementedError("online_size > 1 is not implemented for variant %r" % (self.variant,))
+        self.online_size = int(online_size)
+        self.refresh_kernels()
+        return self
+
+    def _online_kw(self, online_count):
+        """The runtime keyword of the online template memory; nothing at online_size 1."""
+        if self.online_size == 1:
+            if online_count is not None:
+                raise ValueError("online_count needs set_online_size(K) with K > 1")
+            return {}
+        return {"online_count": online_count}
+
     def _runtime(self, device):
         if self._rt is None:
             from .runtime import MixFormerRGBTRuntime
             sd = self.state_dict()
+            kw = {"online_size": self.online_size} if self.online_size > 1 else {}
             with torch.cuda.device(device):
-                self._rt = MixFormerRGBTRuntime(sd, self.variant, dtype=self.compute_dtype, device=device)
+                self._rt = MixFormerRGBTRuntime(sd, self.variant, dtype=self.compute_dtype, device=device, **kw)
         return self._rt
 
     def forward(self, template, online_template, search, run_score_head=False, gt_bboxes=None, return_features=False,
-                **train_kw):
+                online_count=None, **train_kw):
         for nm, x in (("template", template), ("online_template", online_template), ("search", search)):
             if not isinstance(x, (list, tuple)) or len(x) != 2:
                 raise ValueError("%s must be a list [rgb, tir] of (B,3,H,W) tensors" % nm)
         dev = search[0].device
+        if self.training and torch.is_grad_enabled() and (self.online_size > 1 or online_count is not None):
+            raise NotImplementedError("training (module_forward) is not implemented for online_size > 1")
         if self.training and torch.is_grad_enabled():
             # training (the reference actor, DDP + SyncBN wrap this module unchanged): autograd over
             # the HIP ops of mmt_amd.train; `train_ops` may be replaced only by test stand-ins
@@ -391,7 +416,8 @@ class _HipTracker(nn.Module):
         score = bool(run_score_head) and self.variant == "asym_online"
         with torch.cuda.device(dev):
             box, sc = rt.forward(template, online_template, search, run_score_head=score,
-                                 use_graph=self.use_hip_graph, ce_template_mask=getattr(self, "_mask", None))
+                                 use_graph=self.use_hip_graph, ce_template_mask=getattr(self, "_mask", None),
+                                 **self._online_kw(online_count))
             B = box.shape[0]
             coord = box.clone().view(B, 1, 4)
             out = {"pred_boxes": coord}
@@ -412,7 +438,7 @@ class _HipTracker(nn.Module):
     # caches the template tokens' qkv in every block, forward_test runs only the search tokens),
     # defined for the RGB-T models whose own versions are broken (reference defect D2).  Both
     # take [rgb, tir] lists; the result equals forward() on the same template / search.
-    def set_online(self, template, online_template):
+    def set_online(self, template, online_template, online_count=None):
         for nm, x in (("template", template), ("online_template", online_template)):
             if not isinstance(x, (list, tuple)) or len(x) != 2:
                 raise ValueError("%s must be a list [rgb, tir] of (B,3,H,W) tensors" % nm)
@@ -421,10 +447,10 @@ class _HipTracker(nn.Module):
             raise RuntimeError("the MI355X forward needs the inputs on the HIP device (got %s); there is no CPU path" % dev)
         rt = self._runtime(dev)
         with torch.cuda.device(dev):
-            rt.set_template(template, online_template)
+            rt.set_template(template, online_template, **self._online_kw(online_count))
         self._online_batch = template[0].shape[0]
 
-    def forward_test(self, search, run_score_head=False, gt_bboxes=None):
+    def forward_test(self, search, run_score_head=False, gt_bboxes=None, online_count=None):
         if not isinstance(search, (list, tuple)) or len(search) != 2:
             raise ValueError("search must be a list [rgb, tir] of (B,3,H,W) tensors")
         if getattr(self, "_online_batch", None) != search[0].shape[0]:
@@ -433,7 +459,7 @@ class _HipTracker(nn.Module):
         rt = self._runtime(dev)
         score = bool(run_score_head) and self.variant == "asym_online"
         with torch.cuda.device(dev):
-            box, sc = rt.forward_search(search, run_score_head=score)
+            box, sc = rt.forward_search(search, run_score_head=score, **self._online_kw(online_count))
             coord = box.clone().view(-1, 1, 4)
             out = {"pred_boxes": coord}
             if score:

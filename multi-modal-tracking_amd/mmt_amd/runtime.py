@@ -40,7 +40,7 @@ def _ptr(t, off=0):
 
 
 class Dims:
-    def __init__(self, sd, variant):
+    def __init__(self, sd, variant, online_size=1):
         pre = "backbone_v." if variant == "rgbt" else "backbone."
         self.C = sd[pre + "pos_embed_s"].shape[-1]
         self.H = self.C // 64
@@ -53,7 +53,11 @@ class Dims:
         self.gs = int(round(self.ns ** 0.5))
         self.patch = 16
         self.ht, self.hs = self.gt * self.patch, self.gs * self.patch
-        self.n_t = 2 * self.nt1
+        # template rows per sequence: the template and online_size online templates (mixformer_vit_online.py's
+        # ONLINE_SIZES; 1 = the RGB-T fork's one online template), nt1 rows each
+        self.online_size = int(online_size)
+        self.n_t = (1 + self.online_size) * self.nt1
+        self.n_kv1 = 2 * self.nt1  # rows of the score head's second memory: the first template of both modalities
         self.ntok = self.n_t + self.ns
         self.hidden = sd[pre + "blocks.0.mlp.fc1.weight"].shape[0]
         self.nmod = 1 if variant == "rgb" else 2  # modalities (sequences per frame)
@@ -81,13 +85,22 @@ class MixFormerRGBTRuntime:
     SPLITK_TICKETS = 1 << 16
 
     def __init__(self, state_dict, variant, dtype=torch.bfloat16, device="cuda", fold_ln=None, ce=None, head_dtype=None,
-                 ce_mask_count=None):
+                 ce_mask_count=None, online_size=1):
         """fold_ln (default: on for bf16): the ViT's LayerNorms are folded into the qkv / fc1 GEMMs
         (mmt_gemm_params.ln_fold) and the residual-producing GEMMs also write the bf16 copy of the
         residual stream those GEMMs read, so no LayerNorm launch or normalised tensor remains.
         The fp32 path keeps the explicit LayerNorm kernels."""
         if variant not in VARIANTS:
             raise ValueError("unknown variant %r" % (variant,))
+        # online_size K > 1: the online template memory (DESIGN.md "Online template memory").  online_template is
+        # (B, K, 3, h, h) per modality, online_count (B,) in 1..K says how many of a sequence's slots are filled,
+        # and every attention launch reads the valid template rows per sequence from the workspace's TL buffer
+        # (mmt_mam_attention_tl), so one plan and one hipGraph serve every fill level.  1: today's runtime.
+        if int(online_size) != online_size or online_size < 1:
+            raise ValueError("online_size must be an integer >= 1, got %r" % (online_size,))
+        if online_size > 1 and variant in ("asym_ce", "rgb"):
+            raise NotImplementedError("online_size > 1 is not implemented for variant %r (candidate elimination and "
+                                      "the RGB-only model keep one online template)" % (variant,))
         if dtype not in (torch.bfloat16, torch.float16, torch.float32):
             raise ValueError("dtype must be torch.bfloat16, torch.float16 or torch.float32")
         if dtype == torch.bfloat16 and variant == "rgb":
@@ -119,7 +132,7 @@ class MixFormerRGBTRuntime:
             raise ValueError("the LayerNorm fold needs the 16-bit (LDS-DMA) GEMM kernels")
         self.device = torch.device(device)
         sd = {k: v.detach() for k, v in state_dict.items()}
-        self.d = Dims(sd, variant)
+        self.d = Dims(sd, variant, online_size)
         if self.d.C % 256 or self.d.d_model != 512 or self.d.C // 64 * 64 != self.d.C:
             raise ValueError("unsupported dims C=%d d_model=%d" % (self.d.C, self.d.d_model))
         self.w = {}
@@ -167,8 +180,8 @@ class MixFormerRGBTRuntime:
         for pre in pres:
             bb = {"patch_w": self._T(sd[pre + "patch_embed.proj.weight"].reshape(C, -1)),
                   "patch_b": self._F(sd[pre + "patch_embed.proj.bias"]),
-                  "pos": self._F(torch.cat([sd[pre + "pos_embed_t"][0], sd[pre + "pos_embed_t"][0],
-                                            sd[pre + "pos_embed_s"][0]], 0)),
+                  "pos": self._F(torch.cat([sd[pre + "pos_embed_t"][0]] * (1 + d.online_size)
+                                           + [sd[pre + "pos_embed_s"][0]], 0)),
                   "blocks": []}
             for i in range(d.depth):
                 b = pre + "blocks.%d." % i
@@ -358,7 +371,8 @@ class MixFormerRGBTRuntime:
         ws = {
             "B": B,
             "in_t": [e(B, 3, d.ht, d.ht, t=f32) for _ in range(d.nmod)],
-            "in_o": [e(B, 3, d.ht, d.ht, t=f32) for _ in range(d.nmod)],
+            "in_o": [e(B, 3, d.ht, d.ht, t=f32) if d.online_size == 1 else e(B, d.online_size, 3, d.ht, d.ht, t=f32)
+                     for _ in range(d.nmod)],
             "in_s": [e(B, 3, d.hs, d.hs, t=f32) for _ in range(d.nmod)],
             "PATCH": e(R, 3 * d.patch * d.patch), "X": e(R, C, t=f32), "XN": e(R, C), "QKV": e(R, 3 * C),
             "AO": e(R, C), "HID": e(R, d.hidden), "XT": e(R, C),
@@ -381,7 +395,7 @@ class MixFormerRGBTRuntime:
             ws.update({"CAT1": e(B * ns, 2 * C), "CAT2": e(B * ns, C)})
         if self.variant == "asym_online":
             ws.update({"ROIT": e(B * 16, C, t=f32), "KV0": e(B * 16, 2 * C, t=f32), "AT": e(B, C, t=f32),
-                       "XS": e(B, C, t=f32), "Q1": e(B, C, t=f32), "KV1": e(B * d.n_t, 2 * C, t=f32),
+                       "XS": e(B, C, t=f32), "Q1": e(B, C, t=f32), "KV1": e(B * d.n_kv1, 2 * C, t=f32),
                        "M1": e(B, C, t=f32), "M2": e(B, C, t=f32), "SC": e(B, 1, t=f32)})
         if self.ce:
             nparts = d.H * (2 * d.n_t // 8)  # (the 16-bit types use 16-query blocks: half of it)
@@ -393,6 +407,8 @@ class MixFormerRGBTRuntime:
                        "CEO": e(S, ns, t=torch.int32), "CEI": e(S, ns, t=torch.int32),
                        "CEM": [e(B, 2 * ns, t=f32) for _ in self.ce],
                        "CEMASK": torch.ones(B, 2 * d.n_t, device=dev, dtype=torch.uint8)})
+        if d.online_size > 1:  # valid template rows per sequence, read by every attention launch; all slots filled
+            ws["TL"] = torch.full((S,), d.n_t, device=dev, dtype=torch.int32)
         ws["plan"] = self._build_plan(ws, False)
         if self.variant == "asym_online":
             ws["plan_score"] = self._build_plan(ws, True)
@@ -526,8 +542,12 @@ class MixFormerRGBTRuntime:
         hand = fold and not self.ce and C % 64 == 0 and C <= 1024
         nst = 2 * (C // 64)
         LNST = ws["LNST"]
-        plan.append((LIB.mmt_patch_im2col, self._image_args(ws["in_t"], ws["in_o"], ws["in_s"])
-                     + (P(ws["PATCH"]), B, d.ht, d.hs, d.patch, cdt), "patch_im2col", None))
+        if d.online_size == 1:
+            plan.append((LIB.mmt_patch_im2col, self._image_args(ws["in_t"], ws["in_o"], ws["in_s"])
+                         + (P(ws["PATCH"]), B, d.ht, d.hs, d.patch, cdt), "patch_im2col", None))
+        else:
+            plan.append((LIB.mmt_patch_im2col_mem, self._image_args(ws["in_t"], ws["in_o"], ws["in_s"])
+                         + (P(ws["PATCH"]), B, d.online_size, d.ht, d.hs, d.patch, cdt), "patch_im2col", None))
         KP = 3 * d.patch * d.patch
         gm = B * nr  # rows per modality group
         pat = lambda g: P(ws["PATCH"], (g * B * ntok + off) * KP)  # noqa: E731  (im2col rows: [S][ntok])
@@ -593,7 +613,10 @@ class MixFormerRGBTRuntime:
             ap.scale = 1.0 / LOG2E if self.fold_ln else (C // d.H) ** -0.5  # see q_scale
             ap.q_part = {None: 0, "t": 1, "s": 2}[part]
             ap.impl = self.attn_impl
-            plan.append((LIB.mmt_mam_attention, (ctypes_byref(ap), cdt), "mam_attention", ap))
+            if d.online_size == 1:
+                plan.append((LIB.mmt_mam_attention, (ctypes_byref(ap), cdt), "mam_attention", ap))
+            else:
+                plan.append((LIB.mmt_mam_attention_tl, (ctypes_byref(ap), P(ws["TL"]), cdt), "mam_attention", ap))
             cpx = dict(c2=rows(XN, C), c2_copy=1) if fold else {}
             if hand:
                 cpx["ln_stats_out"] = rows(LNST, nst)
@@ -877,14 +900,38 @@ class MixFormerRGBTRuntime:
             if st != 0:
                 check(st, name)
 
+    def load_online_count(self, ws, online_count):
+        """online_size > 1: TL[m * B + b] = (1 + online_count[b]) * nt1, the valid template rows of every sequence,
+        written on the current stream.  online_count: (B,) integers in 1..online_size -- a list, a host tensor
+        (both checked) or a device tensor (not read back: a value outside the range makes the attention skip
+        that sequence); None leaves TL as it is (all slots filled in a new workspace)."""
+        d = self.d
+        if d.online_size == 1:
+            if online_count is not None:
+                raise ValueError("online_count belongs to a runtime built with online_size > 1")
+            return
+        if online_count is None:
+            return
+        B = ws["B"]
+        c = torch.as_tensor(online_count)
+        if tuple(c.shape) != (B,) or c.dtype.is_floating_point or c.dtype == torch.bool:
+            raise ValueError("online_count must be %d integers, got %s %s" % (B, tuple(c.shape), c.dtype))
+        if c.device.type == "cpu" and (int(c.min()) < 1 or int(c.max()) > d.online_size):
+            raise ValueError("online_count must lie in 1..%d, got %s" % (d.online_size, c.tolist()))
+        tl = (c.to(device=self.device, dtype=torch.int32, non_blocking=True) + 1) * d.nt1
+        ws["TL"].view(d.nmod, B).copy_(tl[None, :].expand(d.nmod, B))
+
     def load_inputs(self, ws, template, online_template, search):
         for dst, src in zip(ws["in_t"] + ws["in_o"] + ws["in_s"], list(template) + list(online_template) + list(search)):
             if src.shape != dst.shape:
                 raise ValueError("input shape %s, expected %s" % (tuple(src.shape), tuple(dst.shape)))
             dst.copy_(src, non_blocking=True)
 
-    def forward(self, template, online_template, search, run_score_head=False, use_graph=False, ce_template_mask=None):
+    def forward(self, template, online_template, search, run_score_head=False, use_graph=False, ce_template_mask=None,
+                online_count=None):
         """template / online_template / search: [rgb, tir] lists of (B,3,H,W) fp32 device tensors.
+        online_size K > 1: online_template is (B,K,3,h,h) per modality and online_count (load_online_count) says
+        how many of each sequence's slots are filled; the images of the other slots are never read as keys.
         ce_template_mask: (B, 2 n_t) bool template-query mask of the candidate elimination (a runtime
         built with ce_mask_count; each row must select that many queries).
         Returns (boxes_cxcywh (B,4) fp32, scores (B,) fp32 or None) — views of the workspace."""
@@ -892,6 +939,7 @@ class MixFormerRGBTRuntime:
         ws = self.workspace(B)
         score = bool(run_score_head) and self.variant == "asym_online"
         self.load_inputs(ws, template, online_template, search)
+        self.load_online_count(ws, online_count)
         self._load_ce_mask(ws, ce_template_mask)
         if use_graph:
             g = self._graphs.get((B, score))
@@ -943,16 +991,18 @@ class MixFormerRGBTRuntime:
                 ws["plan_s_score" if score else "plan_s"] = plan
         return ws
 
-    def set_template(self, template, online_template):
+    def set_template(self, template, online_template, online_count=None):
         """Template pass: template + online template ([rgb, tir] lists of (B,3,h,h) fp32 device
         tensors) through the backbone, filling the per-layer K/V cache (and the final template
-        token states the score head reads)."""
+        token states the score head reads).  online_size K > 1: online_template (B,K,3,h,h) and online_count
+        as forward()'s; the cache rows [0, TL) of a sequence are those of a runtime of exactly that size."""
         B = template[0].shape[0]
         ws = self.cache_workspace(B)
         for dst, src in zip(ws["in_t"] + ws["in_o"], list(template) + list(online_template)):
             if src.shape != dst.shape:
                 raise ValueError("input shape %s, expected %s" % (tuple(src.shape), tuple(dst.shape)))
             dst.copy_(src, non_blocking=True)
+        self.load_online_count(ws, online_count)
         self.run_plan(ws["plan_t"])
 
     def _load_ce_mask(self, ws, ce_template_mask):
@@ -966,9 +1016,10 @@ class MixFormerRGBTRuntime:
                 raise ValueError("ce_template_mask shape %s, expected %s" % (tuple(ce_template_mask.shape), tuple(m.shape)))
             m.copy_(ce_template_mask.to(device=m.device, dtype=torch.uint8), non_blocking=True)
 
-    def forward_search(self, search, run_score_head=False, ce_template_mask=None):
+    def forward_search(self, search, run_score_head=False, ce_template_mask=None, online_count=None):
         """Search pass against the cached template (set_template first, same batch size): boxes
-        (B,4) cxcywh and scores as forward() returns them.  ce_template_mask: as forward()'s."""
+        (B,4) cxcywh and scores as forward() returns them.  ce_template_mask: as forward()'s.  online_count
+        (online_size > 1): None keeps the lengths the template pass left."""
         B = search[0].shape[0]
         ws = self.cache_workspace(B)
         score = bool(run_score_head) and self.variant == "asym_online"
@@ -976,6 +1027,7 @@ class MixFormerRGBTRuntime:
             if src.shape != dst.shape:
                 raise ValueError("input shape %s, expected %s" % (tuple(src.shape), tuple(dst.shape)))
             dst.copy_(src, non_blocking=True)
+        self.load_online_count(ws, online_count)
         self._load_ce_mask(ws, ce_template_mask)
         self.run_plan(ws["plan_s_score"] if score else ws["plan_s"])
         return ws["BOX"], (ws["SC"].view(-1) if score else None)
@@ -1027,15 +1079,16 @@ class MixFormerRGBTRuntime:
         es = ws["QKVL"][0].element_size()
         C, ntok = d.C, d.ntok
         img = 3 * d.ht * d.ht * 4
-        gather = [(src, dst, img, img, img, img, 1, img)
-                  for srcs, dsts in ((template, st["in_t"]), (online_template, st["in_o"])) for src, dst in zip(srcs, dsts)]
+        gather = [(src, dst, n * img, n * img, n * img, n * img, 1, n * img)  # n images per slot
+                  for srcs, dsts, n in ((template, st["in_t"], 1), (online_template, st["in_o"], d.online_size))
+                  for src, dst in zip(srcs, dsts)]
         row = 3 * C * es
         scatter = [(_ptr(st["QKVL"][i], m * D * ntok * 3 * C + C), _ptr(ws["QKVL"][i], m * N * ntok * 3 * C + C),
                     ntok * row, ntok * row, row, row, d.n_t, 2 * C * es)
                    for i in range(d.depth) for m in range(d.nmod)]
         if self.variant == "asym_online":
             r1 = 2 * C * 4
-            scatter.append((st["KV1"], ws["KV1"], d.n_t * r1, d.n_t * r1, r1, r1, d.n_t, r1))
+            scatter.append((st["KV1"], ws["KV1"], d.n_kv1 * r1, d.n_kv1 * r1, r1, r1, d.n_kv1, r1))
         slots = torch.full((D,), -1, device=self.device, dtype=torch.int32)
         sc = {"N": N, "D": D, "ws": ws, "stage": st, "slots": slots, "graph": None,
               "keep": (template, online_template)}
@@ -1077,6 +1130,10 @@ class MixFormerRGBTRuntime:
                 raise IndexError("slot list %s of %d slots" % (c, sc["N"]))
         for c in chunks:
             sc["slots"].copy_(torch.tensor(c, dtype=torch.int32), non_blocking=False)
+            if self.d.online_size > 1:  # the staging pass's lengths: those of the chunk's slots (the N-slot TL is the caller's)
+                nm, N, D = self.d.nmod, sc["N"], sc["D"]
+                idx = sc["slots"].clamp(min=0).long()
+                sc["stage"]["TL"].view(nm, D).copy_(sc["ws"]["TL"].view(nm, N).index_select(1, idx))
             if use_graph:
                 if sc["graph"] is None:
                     sc["graph"] = self.capture_plan(sc["plan"])  # capture_plan runs the plan once before recording it
@@ -1105,6 +1162,8 @@ class MixFormerRGBTRuntime:
         if not 1 <= R <= N:
             raise ValueError("packed step needs 1 <= R <= N slots, got R=%d N=%d" % (R, N))
         d = self.d
+        if d.online_size > 1:
+            raise NotImplementedError("the packed step (slot_pack_gather) is not implemented for online_size > 1")
         if template is not None:
             ws = self.workspace(R, ws_key)
             img = 3 * d.ht * d.ht * 4
@@ -1133,18 +1192,22 @@ class MixFormerRGBTRuntime:
                     for i in range(d.depth) for m in range(d.nmod)]
             if self.variant == "asym_online":
                 r1 = 2 * C * 4
-                segs.append((src_ws["KV1"], ws["KV1"], d.n_t * r1, d.n_t * r1, r1, r1, d.n_t, r1))
+                segs.append((src_ws["KV1"], ws["KV1"], d.n_kv1 * r1, d.n_kv1 * r1, r1, r1, d.n_kv1, r1))
         tab, smax = self._slot_table(segs)
         return ws, [(LIB.mmt_slot_copy, (_ptr(tab), len(segs), _ptr(slot_list), N, None, R, R, smax), "pack_gather", tab)]
 
-    def plan_for_inputs(self, template, online_template, search, run_score_head=False, part=None, ws_key=None):
+    def plan_for_inputs(self, template, online_template, search, run_score_head=False, part=None, ws_key=None,
+                        online_count=None):
         """The plan of batch B with its patch staging reading the given device tensors directly
         (zero-copy: for frames already resident in HBM, e.g. written there by the preprocessing).
         part None: the full forward; "t": the template pass (search may be None); "s": the search
         pass against the cache (template / online_template may be None).  ws_key: the plan of a second,
-        separate workspace of batch B (workspace's key; default: the batch's own)."""
+        separate workspace of batch B (workspace's key; default: the batch's own).  online_size > 1: the plan's
+        attention reads that workspace's TL buffer (ws["TL"], int32 [nmod * B]); online_count writes it here
+        (load_online_count), and a caller may rewrite it between replays."""
         B = (search if part == "s" else template)[0].shape[0]
         ws = self.workspace(B, ws_key) if part is None else self.cache_workspace(B, key=ws_key)
+        self.load_online_count(ws, online_count)
         score = bool(run_score_head) and self.variant == "asym_online"
         key = {None: "plan", "t": "plan_t", "s": "plan_s"}[part]
         base = ws[key + "_score" if score and part != "t" else key]

@@ -78,11 +78,22 @@ class RGBTTrackerCore:
 
     network: a built HIP model (mmt_amd.model); multimodal: apply the JET colour map to the TIR
     crops (Preprocessor_Multimodal) or not (Preprocessor_wo_mask); online_score: the
-    asymmetric_shared_online tracker's score-gated online-template update."""
+    asymmetric_shared_online tracker's score-gated online-template update; online_size / max_score_decay:
+    upstream's memory of K online templates and its score decay (online_memory_schedule; online-score tracker
+    only, the network set to the same size with set_online_size)."""
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
-                 multimodal, online_score=False, use_graph=True, kv_cache=False):
+                 multimodal, online_score=False, use_graph=True, kv_cache=False, online_size=1, max_score_decay=1.0):
         self.net = network
+        # online_size K > 1 (online-score tracker): K online templates, filled and replaced by upstream's
+        # score-gated ring (online_memory_schedule).  The step always runs the cached passes, as upstream runs
+        # set_online / forward_test; a promotion writes one template slot and the sequence's length, and replays
+        # the captured template pass: nothing is re-planned or re-captured.  K = 1 with decay 1.0: the code below
+        # as it was.
+        self.online_size, self.max_score_decay = check_online_memory(online_size, max_score_decay, online_score, network)
+        self._ring = self.online_size > 1 or self.max_score_decay != 1.0
+        self.online_count, self.forget_id = 1, 0
+        kv_cache = kv_cache or self.online_size > 1
         # kv_cache: the template tokens' per-layer qkv are computed once per template update (a
         # separate template pass) and each frame runs only the search tokens (runtime.cache_workspace);
         # off by default: no faster at batch 1 (lib/test/tracker/_rgbt.py KV_CACHE_DEFAULT)
@@ -100,6 +111,8 @@ class RGBTTrackerCore:
         self.state = e(4, dt=torch.float64)
         self.template = [e(1, 3, self.ts, self.ts) for _ in range(2)]
         self.online_template = [e(1, 3, self.ts, self.ts) for _ in range(2)]
+        if self.online_size > 1:
+            self.online_template = [torch.zeros(1, self.online_size, 3, self.ts, self.ts, device=dev) for _ in range(2)]
         self.online_max_template = [e(1, 3, self.ts, self.ts) for _ in range(2)]
         self.search = [e(1, 3, self.ss, self.ss) for _ in range(2)]
         self.search_crop = e(2, 4, dt=torch.float64)
@@ -175,6 +188,8 @@ class RGBTTrackerCore:
         if self._plan is None or (self.use_graph and self._graph is None):
             self._build_step()
         if self.kv_cache and self._tmpl_dirty:  # template pass after a template / online-template change
+            if self.online_size > 1:  # the filled slots: read from device memory by the captured passes
+                self._rt.load_online_count(self._ws, [self.online_count])
             if self._tmpl_graph is not None:
                 self._tmpl_graph.replay()
             else:
@@ -191,13 +206,18 @@ class RGBTTrackerCore:
         self.state.copy_(torch.tensor([float(v) for v in init_bbox], dtype=torch.float64))
         self._crop_templates(self.template, self.state)
         for m in range(2):
-            self.online_template[m].copy_(self.template[m])
+            if self.online_size > 1:  # slot 0 = the template (upstream :68); the other slots are not read yet
+                self.online_template[m].zero_()
+                self.online_template[m][:, 0].copy_(self.template[m])
+            else:
+                self.online_template[m].copy_(self.template[m])
             # reference defect D6 (asymmetric_shared_online.py:115): online_max_template is read
             # before it is ever assigned if no frame scores > 0.5 before the first update frame;
             # here it starts as the template instead of raising AttributeError
             self.online_max_template[m].copy_(self.template[m])
         self.frame_id = 0
         self.max_pred_score = -1.0
+        self.online_count, self.forget_id = 1, 0
         self._tmpl_dirty = True
         self._check_crop(self.tmpl_crop)
 
@@ -206,7 +226,22 @@ class RGBTTrackerCore:
         self._load_frames(image)
         self.frame_id += 1
         self._step()
-        if self.online_score:
+        if self._ring:
+            pred_score = torch.sigmoid(self._ws["SC"].view(1)).item()
+            crop, writes, (self.online_count, self.forget_id, self.max_pred_score) = online_memory_schedule(
+                self.frame_id, self.update_intervals, pred_score, (self.online_count, self.forget_id, self.max_pred_score),
+                self.online_size, self.max_score_decay)
+            if crop:
+                self._crop_templates(self.online_max_template, self.state)
+            for j, slot in enumerate(writes):  # the first from the candidate, any further one from the template
+                src = self.online_max_template if j == 0 else self.template
+                for m in range(2):
+                    (self.online_template[m][:, slot] if self.online_size > 1 else self.online_template[m]).copy_(src[m])
+            if writes:
+                for m in range(2):
+                    self.online_max_template[m].copy_(self.template[m])
+                self._tmpl_dirty = True
+        elif self.online_score:
             pred_score = torch.sigmoid(self._ws["SC"].view(1)).item()
             if pred_score > 0.5 and pred_score > self.max_pred_score:
                 self._crop_templates(self.online_max_template, self.state)
@@ -261,6 +296,51 @@ def template_schedule(online_score, frame_id, update_intervals, pred_score=None,
     if due:
         max_pred_score = -1
     return crop, due, max_pred_score
+
+
+def online_memory_schedule(frame_id, update_intervals, pred_score, memory, online_size, max_score_decay=1.0):
+    """The online-score tracker's frame with a memory of online_size online templates (upstream
+    lib/test/tracker/mixformer_vit_online.py:107-129), as a pure function of one sequence's counters.
+    memory = (count, forget_id, max_pred_score): the filled slots (1 after initialize, the template's copy in
+    slot 0, :68), the ring's next victim, and the best score since the last update.  Per frame: the best score
+    decays; the score gate (pred_score > 0.5 and > max_pred_score) makes the crop at the new state the candidate;
+    then every interval that divides frame_id, in order, appends the candidate while count < online_size, else
+    overwrites slot forget_id and advances the ring, and resets the candidate to the template and the best
+    score to -1 (so a second interval on the same frame stores the template itself).
+    Returns (crop, writes, memory'): writes = the slots written, the first from the candidate, any further one
+    from the template.  online_size 1 with decay 1.0 makes template_schedule's decisions (writes = [0] * due)."""
+    count, forget_id, max_pred_score = memory
+    max_pred_score = max_pred_score * max_score_decay
+    crop = pred_score > 0.5 and pred_score > max_pred_score
+    if crop:
+        max_pred_score = pred_score
+    writes = []
+    for i in update_intervals:
+        if frame_id % i == 0:
+            if count < online_size:
+                writes.append(count)
+                count += 1
+            else:
+                writes.append(forget_id)
+                forget_id = (forget_id + 1) % online_size
+            max_pred_score = -1
+    return crop, writes, (count, forget_id, max_pred_score)
+
+
+def check_online_memory(online_size, max_score_decay, online_score, network=None):
+    """The trackers' online_size / max_score_decay arguments: (K, decay) or ValueError."""
+    K, decay = int(online_size), float(max_score_decay)
+    if K != online_size or K < 1:
+        raise ValueError("online_size must be an integer >= 1, got %r" % (online_size,))
+    if not 0.0 < decay <= 1.0:
+        raise ValueError("max_score_decay must lie in (0, 1], got %r" % (max_score_decay,))
+    if not online_score and (K > 1 or decay != 1.0):
+        raise ValueError("online_size > 1 and max_score_decay belong to the online-score tracker: the plain trackers "
+                         "re-crop their one online template and have no upstream ring")
+    if network is not None and getattr(network, "online_size", 1) != K:
+        raise ValueError("the network was built for online_size %d, the tracker asks for %d (network.set_online_size)"
+                         % (getattr(network, "online_size", 1), K))
+    return K, decay
 
 
 def pack_rungs(pack, slots):
@@ -344,7 +424,14 @@ class RGBTBatchTrackerCore:
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
                  multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1, slot_cache=False,
-                 refresh_slots=None, pack=None):
+                 refresh_slots=None, pack=None, online_size=1, max_score_decay=1.0):
+        # online_size K > 1: count and ring per slot (online_memory_schedule), slot_cache on or off; the step
+        # graph reads every slot's valid template rows from the workspace's TL buffer, so slots at different
+        # fill levels share one replay.  Not with pack.
+        self.online_size, self.max_score_decay = check_online_memory(online_size, max_score_decay, online_score, network)
+        self._ring = self.online_size > 1 or self.max_score_decay != 1.0
+        if self.online_size > 1 and pack:
+            raise ValueError("pack (steps sized to the active slots) is not implemented for online_size > 1")
         if kv_cache:
             raise NotImplementedError("kv_cache is the whole-batch template pass, the batched tracker's template "
                                       "updates are per slot: use slot_cache=True (the per-slot template K/V cache)")
@@ -373,6 +460,10 @@ class RGBTBatchTrackerCore:
         self.state = z(N, 4, dt=torch.float64)
         self.template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
         self.online_template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
+        if self.online_size > 1:
+            self.online_template = [z(N, self.online_size, 3, self.ts, self.ts) for _ in range(2)]
+        self.online_count, self.forget_id = [1] * N, [0] * N
+        self._counts_dirty = True  # the host counts differ from the runtime's TL buffer
         self.online_max_template = [z(N, 3, self.ts, self.ts) for _ in range(2)]
         self.search = [z(N, 3, self.ss, self.ss) for _ in range(2)]
         self.search_crop = z(N, 2, 4, dt=torch.float64)
@@ -395,7 +486,7 @@ class RGBTBatchTrackerCore:
         self._tmpl_dst = self.online_max_template if self.online_score else self.online_template
         self._fview = [None] * N  # per slot the (H, W, 3) views of its frame buffers
         self._readback = [self.state.view(-1), self.search_crop[:, 0, 2]]  # what a step returns to the host
-        self._graph = self._plan = self._rt = self._ws = None
+        self._graph = self._plan = self._rt = self._ws = self._ws_tl = None
         self.last_scores = None  # online-score tracker: every slot's sigmoid(score) of the last step
         if self.slot_cache:  # the runtime's refusal, here rather than at the first track
             from .runtime import refuse_cache_with_ce
@@ -537,6 +628,9 @@ class RGBTBatchTrackerCore:
             if pk["members"] != self._act:
                 pk["list"].copy_(torch.tensor(pack_list(self._act, R), dtype=torch.int32))
                 pk["members"] = list(self._act)
+        if self.online_size > 1 and (self._counts_dirty or self._ws_tl is not self._ws):
+            self._rt.load_online_count(self._ws, self.online_count)  # before the refresh: its staging pass reads them
+            self._counts_dirty, self._ws_tl = False, self._ws
         if self._dirty:  # slot cache: template pass of the slots whose templates changed
             self.refresh_replays += self._rt.refresh_template_slots(self._sc, sorted(self._dirty), self.use_graph)
             self._dirty.clear()
@@ -570,9 +664,15 @@ class RGBTBatchTrackerCore:
             src = self._tmpl_dst[m][b]
             for dst in (self.template, self.online_template, self.online_max_template):
                 if dst is not self._tmpl_dst:  # the candidate starts as the template (reference defect D6)
-                    dst[m][b].copy_(src)
+                    if dst is self.online_template and self.online_size > 1:  # slot 0; the others are not read yet
+                        dst[m][b].zero_()
+                        dst[m][b, 0].copy_(src)
+                    else:
+                        dst[m][b].copy_(src)
         self.frame_id[b] = 0
         self.max_pred_score[b] = -1.0
+        self.online_count[b], self.forget_id[b] = 1, 0
+        self._counts_dirty = True
         self._set_active(b, True)
         if self.slot_cache:
             self._dirty.add(b)
@@ -610,7 +710,7 @@ class RGBTBatchTrackerCore:
             for j, b in enumerate(act):
                 scores[b] = vals[5 * N + j]
             vals[5 * N:] = scores
-        out, crop, promote = {}, [], []
+        out, crop, promote, writes = {}, [], [], []
         for b in act:
             if vals[4 * N + b] < 1:
                 self.release(b)
@@ -618,6 +718,15 @@ class RGBTBatchTrackerCore:
                 continue
             out[b] = vals[4 * b:4 * b + 4]
             score = vals[5 * N + b] if self.online_score else None
+            if self._ring:
+                c, w, (self.online_count[b], self.forget_id[b], self.max_pred_score[b]) = online_memory_schedule(
+                    self.frame_id[b], self.update_intervals, score,
+                    (self.online_count[b], self.forget_id[b], self.max_pred_score[b]), self.online_size, self.max_score_decay)
+                if c:
+                    crop.append(b)
+                if w:
+                    writes.append((b, w))
+                continue
             c, p, self.max_pred_score[b] = template_schedule(self.online_score, self.frame_id[b], self.update_intervals,
                                                              score, self.max_pred_score[b])
             if c:
@@ -639,6 +748,16 @@ class RGBTBatchTrackerCore:
                 if twice:  # a second interval on the same frame promotes the reset candidate
                     i2 = torch.tensor(twice, device=self.dev)
                     self.online_template[m][i2] = self.template[m][i2]
+        if writes:  # the ring: per slot the first write takes the candidate, any further one the template
+            if self.slot_cache:
+                self._dirty.update(b for b, _ in writes)
+            self._counts_dirty = True
+            for m in range(2):
+                for b, w in writes:
+                    for j, slot in enumerate(w):
+                        src = self.online_max_template if j == 0 else self.template
+                        (self.online_template[m][b, slot] if self.online_size > 1 else self.online_template[m][b]).copy_(src[m][b])
+                    self.online_max_template[m][b].copy_(self.template[m][b])
         return out
 
 
