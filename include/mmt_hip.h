@@ -656,6 +656,44 @@ int mmt_track_update_packed(const float* pred_cxcywh, const double* crop, int cr
                             const int32_t* hw, const uint8_t* active, const int32_t* slot_list_dev, int n, int slots,
                             int search_size, double margin, void* stream);
 
+/* RGB-D input: the reference's per-frame host preparation of a raw 16-bit depth frame
+ * (lib/test/evaluation/depth_utils.py:17-22, :55-60; get_rgbd_frame(dtype="rgb3d", depth_clip=True)),
+ * on the device, written into the tracker's second-modality frame buffer.  For d = depth[H][W], n = H * W
+ * and s the sorted pixels: k0 = (n-1)/2, k1 = n/2, capi = min((3 * (s[k0] + s[k1])) >> 1, 10000) (numpy's
+ * median, times 3, capped, truncated into uint16); d' = min(d, capi); smin / smax = min / max of d';
+ * cv2.normalize(NORM_MINMAX, 0..255): scale = 255 * (smax - smin > DBL_EPSILON ? 1 / (smax - smin) : 0) and
+ * shift = 0 - smin * scale in float64, a = (float)scale, b = (float)shift, then per pixel
+ * fl32(fl32((float)d' * a) + b) (two roundings, never fused), rounded half to even, saturated to 0..65535,
+ * low 8 bits (the uint8 cast); out[y][x][0..2] all equal it.  mmt_amd/depth.py:depth_to_3xd restates this in
+ * numpy, bit for bit.  The median is an exact selection by integer counts: results do not depend on the order
+ * atomics arrive in.
+ *   depth   [H][W] uint16, device memory (2-byte aligned; 16-byte aligned frames take the 16-byte path)
+ *   out     [H][W][3] uint8
+ *   work    MMT_DEPTH_WORK_BYTES of device memory per entry (4-byte aligned), entries must not share it; it is
+ *           cleared by the first launch of every call, so it needs no initialisation and a captured call replays
+ *   record  NULL or 7 int32: s[k0], s[k1], capi, smin, smax, then the float bits of a and b
+ * One call is five launches (clear, high-byte histogram with min / max, low-byte counts inside the buckets of the
+ * two ranks, a one-wave finalise, the per-pixel pass); every grid depends on n alone, the kernels loop over H * W.
+ * Nothing is read back, allocated or synchronised on the host.
+ * mmt_depth_prepare: n <= MMT_MAX_CROPS host descriptors.  MMT_EBADARG (before any launch): p NULL, n outside
+ * 1..MMT_MAX_CROPS, a NULL depth / out / work, H <= 0, W <= 0, H * W >= 2^32 (the counts are uint32), a misaligned
+ * depth / work / record.
+ * mmt_depth_prepare_table: the descriptors in DEVICE memory (table_dev[n], 8-byte aligned), enable_dev NULL or n
+ * bytes as in mmt_sample_target_table: a captured call holds only the two pointers, so the host re-points or
+ * re-sizes an entry with a small copy between replays.  An entry is SKIPPED -- none of out / work / record is
+ * written -- when its enable byte is 0 or it holds anything the host form rejects.  Per-entry arithmetic as the
+ * host form, bit for bit.  MMT_EBADARG (before any launch): table_dev NULL or misaligned, n <= 0, n > 65535. */
+#define MMT_DEPTH_WORK_BYTES 4096
+typedef struct {
+    const uint16_t* depth;
+    int32_t H, W;
+    uint8_t* out;
+    void* work;
+    int32_t* record;
+} mmt_depth_params;
+int mmt_depth_prepare(const mmt_depth_params* p, int n, void* stream);
+int mmt_depth_prepare_table(const mmt_depth_params* table_dev, const uint8_t* enable_dev, int n, void* stream);
+
 /* Slot-indexed row copy (the batched tracker's per-slot template K/V cache).  A segment describes one
  * strided 2-D block per slot on each side: slot s, row r occupies row_bytes bytes at
  * base + s * slot_stride + r * row_pitch.  For every list entry j < n and every segment, the block of

@@ -14,6 +14,7 @@ Each module also has `get_batch_tracker_class()`: the same tracker for `slots` s
 """
 import torch
 
+from mmt_amd.depth import check_aux_format
 from mmt_amd.tracking import RGBTBatchTrackerCore, RGBTTrackerCore, check_online_memory
 
 try:  # the reference's BaseTracker (with its visdom helpers) when its lib/ is overlaid
@@ -46,10 +47,18 @@ def _online_memory(params, online_score):
     return {"online_size": K, "max_score_decay": decay}
 
 
+def _aux_format(params):
+    """params.aux_format: "rgb8" (default: image[1] is a (H, W, 3) uint8 frame) or "depth16" (RGB-D: image[1] is the
+    raw (H, W) uint16 depth frame, prepared on the device as the reference's get_rgbd_frame(dtype="rgb3d",
+    depth_clip=True) prepares it on the host).  Checked before the network is built."""
+    return check_aux_format(getattr(params, "aux_format", "rgb8"))
+
+
 def make_tracker_class(builder, multimodal, online_score=False, kv_cache=KV_CACHE_DEFAULT):
     class MixFormer(BaseTracker):
         def __init__(self, params, dataset_name):
             super().__init__(params)
+            aux_format = _aux_format(params)
             memory = _online_memory(params, online_score)
             network = builder(params.cfg, train=False)
             if getattr(params, "checkpoint", None):
@@ -65,7 +74,7 @@ def make_tracker_class(builder, multimodal, online_score=False, kv_cache=KV_CACH
             self.core = RGBTTrackerCore(self.network, params.template_factor, params.template_size,
                                         params.search_factor, params.search_size, self.update_intervals,
                                         multimodal=multimodal, online_score=online_score,
-                                        kv_cache=getattr(params, "kv_cache", kv_cache), **memory)
+                                        kv_cache=getattr(params, "kv_cache", kv_cache), aux_format=aux_format, **memory)
             self.state = None
             self.frame_id = 0
 
@@ -114,6 +123,7 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
             if getattr(params, "save_all_boxes", False):
                 raise NotImplementedError("save_all_boxes is not supported by the batched tracker")
             self.params = params
+            aux_format = _aux_format(params)
             memory = _online_memory(params, online_score)
             if memory["online_size"] > 1 and getattr(params, "pack_slots", None):
                 raise ValueError("pack_slots is not implemented for online_size > 1")
@@ -134,7 +144,7 @@ def make_batch_tracker_class(builder, multimodal, online_score=False):
                                              kv_cache=getattr(params, "kv_cache", False), slots=self.slots,
                                              slot_cache=getattr(params, "slot_cache", False),
                                              refresh_slots=getattr(params, "refresh_slots", None),
-                                             pack=getattr(params, "pack_slots", None), **memory)
+                                             pack=getattr(params, "pack_slots", None), aux_format=aux_format, **memory)
 
         def initialize(self, slot, image, info: dict):
             """image: [image_v, image_i]; info["init_bbox"]: (bbox_v, bbox_i), the RGB box is used."""

@@ -72,6 +72,13 @@ class CropParams(ctypes.Structure):
                 ("lut", vp), ("mean", f32 * 3), ("std", f32 * 3), ("out", vp), ("patch", vp), ("crop", vp)]
 
 
+DEPTH_WORK_BYTES = 4096  # MMT_DEPTH_WORK_BYTES
+
+
+class DepthParams(ctypes.Structure):
+    _fields_ = [("depth", vp), ("H", i32), ("W", i32), ("out", vp), ("work", vp), ("record", vp)]
+
+
 class ConvWprep(ctypes.Structure):
     _fields_ = [("w", vp), ("b", vp), ("wf", vp), ("wb", vp), ("bp", vp), ("cout", i32), ("cp", i32), ("cin", i32),
                 ("pad_", i32)]
@@ -162,6 +169,8 @@ _PROTOS = {
     "mmt_track_update_slots": [vp, vp, i32, vp, vp, vp, i32, i32, f64, vp],
     "mmt_sample_target_packed": [vp, vp, vp, i32, i32, i32, i32, vp, i64, i64, vp],
     "mmt_track_update_packed": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f64, vp],
+    "mmt_depth_prepare": [ctypes.POINTER(DepthParams), i32, vp],
+    "mmt_depth_prepare_table": [vp, vp, i32, vp],
     "mmt_slot_copy": [vp, i32, vp, i32, vp, i32, i32, i64, vp],
     "mmt_adamw_chunk_elems": [],
     "mmt_adamw_step": [vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f32, i32, vp],

@@ -22,6 +22,8 @@ ones carry `register_autograd` formulas built from the registered backward ops:
   mmt::ce_rows_gather / mmt::ce_index_invert    mmt_ce_rows_gather / mmt_ce_index_invert: the pruning and the
                                                 recovery of the fp32 token rows in training; the backward of a
                                                 row gather is the row gather by the inverted index
+  mmt::depth_prepare                            mmt_depth_prepare: a raw 16-bit depth frame clipped, normalised
+                                                and replicated into the tracker's (H, W, 3) uint8 frame
 
 Each *_forward op has its backward registered (register_autograd over the *_backward ops), so
 autograd, FakeTensor and torch.compile see one op per native call.
@@ -427,6 +429,25 @@ def _rows_backward(ctx, dy):
 
 
 ce_rows_gather.register_autograd(_rows_backward, setup_context=_rows_setup)
+
+
+# ------------------------------------------------------------------------------------------- RGB-D input
+@torch.library.custom_op("mmt::depth_prepare", mutates_args=())
+def depth_prepare(depth: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """depth (H, W) uint16 (or int16 as its bit pattern) -> (frame (H, W, 3) uint8, record (7,) int32): the
+    reference's get_rgbd_frame(dtype="rgb3d", depth_clip=True) on the device (mmt_depth_prepare;
+    mmt_amd.depth.depth_to_3xd is its numpy restatement)."""
+    from .depth import prepare_depth
+    _need(depth, "depth", (torch.uint16, torch.int16))
+    if depth.dim() != 2 or depth.numel() == 0:
+        raise RuntimeError("depth_prepare: a non-empty (H, W) frame expected")
+    return prepare_depth(depth)
+
+
+@depth_prepare.register_fake
+def _(depth):
+    H, W = depth.shape
+    return depth.new_empty(H, W, 3, dtype=torch.uint8), depth.new_empty(7, dtype=torch.int32)
 
 
 def mam_attention(qkv, n_t, heads):

@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LIB, CropParams, check
+from ._lib import DEPTH_WORK_BYTES, LIB, CropParams, DepthParams, check
+from .depth import as_depth16, check_aux_format, depth_params
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
@@ -73,6 +74,31 @@ def sample_target(params_list, stream=None):
     return arr
 
 
+def check_depth_frame(x, H, W):
+    """aux_format="depth16": the second frame of a pair as an int16 tensor holding the uint16 bits (as_depth16),
+    of the RGB frame's size; ValueError otherwise."""
+    d = as_depth16(x, "the depth frame")
+    if tuple(d.shape) != (H, W):
+        raise ValueError("the depth frame must be (%d, %d), the RGB frame's size, got %s" % (H, W, tuple(d.shape)))
+    return d
+
+
+def _split_pair(image):
+    """aux_format="depth16": [image_v, image_i] checked as a (H, W, 3) uint8 frame and a (H, W) 16-bit depth
+    frame.  Returns (H, W, rgb, depth) as torch tensors (host or device)."""
+    if not isinstance(image, (list, tuple)) or len(image) != 2:
+        raise ValueError("image must be [image_v, image_i]")
+    ims = [torch.as_tensor(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) and x.dtype != np.uint16 else x
+           for x in image]
+    rgb = ims[0]
+    if not isinstance(rgb, torch.Tensor) or rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.dtype != torch.uint8:
+        raise ValueError("the RGB frame must be a (H, W, 3) uint8 image")
+    H, W = rgb.shape[:2]
+    if H <= 0 or W <= 0:
+        raise ValueError("the RGB frame must be a (H, W, 3) uint8 image")
+    return H, W, rgb, check_depth_frame(ims[1], H, W)
+
+
 class RGBTTrackerCore:
     """Tracking state and per-frame step of one sequence on the current device.
 
@@ -80,10 +106,21 @@ class RGBTTrackerCore:
     crops (Preprocessor_Multimodal) or not (Preprocessor_wo_mask); online_score: the
     asymmetric_shared_online tracker's score-gated online-template update; online_size / max_score_decay:
     upstream's memory of K online templates and its score decay (online_memory_schedule; online-score tracker
-    only, the network set to the same size with set_online_size)."""
+    only, the network set to the same size with set_online_size).
+
+    aux_format: "rgb8" (default): image[1] is a (H, W, 3) uint8 frame.  "depth16" (RGB-D): image[1] is the raw
+    (H, W) depth frame of the RGB frame's size -- numpy uint16, torch uint16, or torch int16 taken as the bit
+    pattern of the uint16 values, on the host or already on the device.  It is copied into a uint16 device buffer
+    and prepared on the device (mmt_amd.depth: clip at 3 x median, min-max normalise, three channels) into the
+    second-modality frame buffer: eagerly before the template crop in `initialize`, as the first launches of
+    the step graph in `track`.  Everything after reads that buffer as it reads an uploaded frame.  The step is
+    then built from the table forms (mmt_depth_prepare_table, mmt_sample_target_table, mmt_track_update_slots,
+    one slot): same arithmetic, and a new frame size rewrites the table entries and keeps the graph."""
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
-                 multimodal, online_score=False, use_graph=True, kv_cache=False, online_size=1, max_score_decay=1.0):
+                 multimodal, online_score=False, use_graph=True, kv_cache=False, online_size=1, max_score_decay=1.0,
+                 aux_format="rgb8"):
+        self.aux_format = check_aux_format(aux_format)
         self.net = network
         # online_size K > 1 (online-score tracker): K online templates, filled and replaced by upstream's
         # score-gated ring (online_memory_schedule).  The step always runs the cached passes, as upstream runs
@@ -124,10 +161,18 @@ class RGBTTrackerCore:
         self._tmpl_graph = None
         self.frame_id = 0
         self.max_pred_score = -1.0
+        if self.aux_format == "depth16":  # device tables of one slot: two crop entries, one depth entry
+            self._dbuf = self._fbuf = self._hw = self._depth = self._depth_host = None
+            self._dwork = torch.empty(DEPTH_WORK_BYTES, device=dev, dtype=torch.uint8)
+            self._search_tab = torch.zeros(2 * ctypes.sizeof(CropParams), device=dev, dtype=torch.uint8)
+            self._depth_tab = torch.zeros(ctypes.sizeof(DepthParams), device=dev, dtype=torch.uint8)
+            self.hw = torch.zeros(1, 2, device=dev, dtype=torch.int32)
 
     # ------------------------------------------------------------------ frames
     def _load_frames(self, image):
         """Copy the two (H, W, 3) uint8 frames (numpy or torch) into fixed device buffers."""
+        if self.aux_format == "depth16":
+            return self._load_depth_pair(image)
         if not isinstance(image, (list, tuple)) or len(image) != 2:
             raise ValueError("image must be [image_v, image_i]")
         ims = [torch.as_tensor(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x for x in image]
@@ -140,6 +185,35 @@ class RGBTTrackerCore:
         for dst, src in zip(self.frames, ims):
             dst.copy_(src, non_blocking=src.device.type == "cuda")
         return H, W
+
+    def _load_depth_pair(self, image):
+        """aux_format="depth16": copy the RGB frame and the raw depth frame into device buffers that only grow;
+        a new frame size rewrites the table entries the step graph reads (the graph itself stays)."""
+        H, W, rgb, depth = _split_pair(image)
+        dev, n = self.dev, H * W
+        if self._dbuf is None or self._dbuf.numel() < n:
+            self._fbuf = [torch.empty(n * 3, device=dev, dtype=torch.uint8) for _ in range(2)]
+            self._dbuf = torch.empty(n, device=dev, dtype=torch.int16)
+            self._hw = None
+        if self._hw != (H, W):
+            self._hw = (H, W)
+            self.frames = [buf[:n * 3].view(H, W, 3) for buf in self._fbuf]
+            self._depth = self._dbuf[:n].view(H, W)
+            self._depth_host = depth_params(self._depth, self.frames[1], self._dwork)
+            crops = (CropParams * 2)(*[crop_params(self.frames[m], self.state, self.sf, self.ss,
+                                                   out=self.search[m].view(-1), crop=self.search_crop[m],
+                                                   lut=self.lut if m == 1 else None) for m in range(2)])
+            self._search_tab.copy_(torch.frombuffer(crops, dtype=torch.uint8))
+            self._depth_tab.copy_(torch.frombuffer(self._depth_host, dtype=torch.uint8))
+            self.hw.copy_(torch.tensor([[H, W]], dtype=torch.int32))
+        self.frames[0].copy_(rgb, non_blocking=rgb.device.type == "cuda")
+        self._depth.copy_(depth, non_blocking=depth.device.type == "cuda")
+        return H, W
+
+    def _prepare_depth(self):
+        """The device preparation of the loaded depth frame into frames[1], eagerly (`initialize`)."""
+        check(LIB.mmt_depth_prepare(ctypes.byref(self._depth_host), 1, torch.cuda.current_stream().cuda_stream),
+              "mmt_depth_prepare")
 
     def _crop_templates(self, dst, box):
         """Both modalities' template crops at `box` (device fp64) into dst[0] / dst[1]."""
@@ -154,10 +228,6 @@ class RGBTTrackerCore:
         # alive, and rebuild when the network swaps it (load_state_dict / .to() / refresh_kernels)
         self._rt = rt
         score = self.online_score
-        H, W = self.frames[0].shape[:2]
-        self._keep = [crop_params(self.frames[m], self.state, self.sf, self.ss, out=self.search[m].view(-1),
-                                  crop=self.search_crop[m], lut=self.lut if m == 1 else None) for m in range(2)]
-        arr = (CropParams * 2)(*self._keep)
         part = "s" if self.kv_cache else None
         model_plan = rt.plan_for_inputs(self.template, self.online_template, self.search, run_score_head=score,
                                         part=part)
@@ -167,10 +237,23 @@ class RGBTTrackerCore:
             self._tmpl_graph = rt.capture_plan(self._tmpl_plan) if self.use_graph else None
             self._tmpl_dirty = True
         self._ws = ws
-        plan = [(LIB.mmt_sample_target, (arr, 2), "track_sample_target", arr)]
-        plan += model_plan
-        plan.append((LIB.mmt_track_update, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), self.state.data_ptr(), 1,
-                                            H, W, self.ss, 10.0), "track_update", None))
+        if self.aux_format == "depth16":  # the table forms over one slot: the frame size lives in device memory
+            plan = [(LIB.mmt_depth_prepare_table, (self._depth_tab.data_ptr(), None, 1), "track_depth_prepare_table", None),
+                    (LIB.mmt_sample_target_table, (self._search_tab.data_ptr(), None, 2, self.ss),
+                     "track_sample_target_table", None)]
+            plan += model_plan
+            plan.append((LIB.mmt_track_update_slots, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), 8,
+                                                      self.state.data_ptr(), self.hw.data_ptr(), None, 1, self.ss, 10.0),
+                         "track_update_slots", None))
+        else:
+            H, W = self.frames[0].shape[:2]
+            self._keep = [crop_params(self.frames[m], self.state, self.sf, self.ss, out=self.search[m].view(-1),
+                                      crop=self.search_crop[m], lut=self.lut if m == 1 else None) for m in range(2)]
+            arr = (CropParams * 2)(*self._keep)
+            plan = [(LIB.mmt_sample_target, (arr, 2), "track_sample_target", arr)]
+            plan += model_plan
+            plan.append((LIB.mmt_track_update, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), self.state.data_ptr(), 1,
+                                                H, W, self.ss, 10.0), "track_update", None))
         self._plan = plan
         if self.use_graph:
             # capture_plan runs the plan once before recording it, and mmt_track_update moves the
@@ -203,6 +286,8 @@ class RGBTTrackerCore:
     # ------------------------------------------------------------------ tracker API
     def initialize(self, image, init_bbox):
         self._load_frames(image)
+        if self.aux_format == "depth16":
+            self._prepare_depth()
         self.state.copy_(torch.tensor([float(v) for v in init_bbox], dtype=torch.float64))
         self._crop_templates(self.template, self.state)
         for m in range(2):
@@ -418,13 +503,22 @@ class RGBTBatchTrackerCore:
     template schedule are what they are without packing.  step_counts: {batch: steps run at it}.  After a
     packed step of the online-score tracker last_scores is NaN for the slots that did not run.
 
+    aux_format="depth16" (default "rgb8": nothing below exists): image[1] of every pair is the raw (H, W) depth
+    frame (numpy uint16, torch uint16, or torch int16 as the bit pattern; host or device) of the RGB frame's size.
+    Each slot has a uint16 depth buffer and a depth descriptor in a device table; mmt_depth_prepare_table over
+    that table is the first node of the full and of every packed step graph, with an enable byte per slot that
+    follows the slot's active flag, and `assign` prepares the slot's first frame eagerly before the template crop.
+    The prepared frame is written into the slot's second frame buffer, so the crops, slot_cache, pack and
+    online_size work as they do on uploaded frames.
+
     Failures: a slot whose search crop side falls below 1 (the reference's "Too small bounding
     box.") is released by `track`, and the returned mapping carries the Exception object in place of
     that slot's box; the other slots are not affected."""
 
     def __init__(self, network, template_factor, template_size, search_factor, search_size, update_intervals,
                  multimodal, online_score=False, use_graph=True, kv_cache=False, slots=1, slot_cache=False,
-                 refresh_slots=None, pack=None, online_size=1, max_score_decay=1.0):
+                 refresh_slots=None, pack=None, online_size=1, max_score_decay=1.0, aux_format="rgb8"):
+        self.aux_format = check_aux_format(aux_format)
         # online_size K > 1: count and ring per slot (online_memory_schedule), slot_cache on or off; the step
         # graph reads every slot's valid template rows from the workspace's TL buffer, so slots at different
         # fill levels share one replay.  Not with pack.
@@ -485,6 +579,15 @@ class RGBTBatchTrackerCore:
         self._search_enable, self._tmpl_enable = z(2 * N, dt=torch.uint8), z(2 * N, dt=torch.uint8)
         self._tmpl_dst = self.online_max_template if self.online_score else self.online_template
         self._fview = [None] * N  # per slot the (H, W, 3) views of its frame buffers
+        if self.aux_format == "depth16":
+            # per slot a uint16 depth buffer (kept as int16 bits) and a depth descriptor: entry b prepares slot b's
+            # depth frame into its second frame buffer; its enable byte follows the slot's active flag
+            self._dbuf, self._dview = [None] * N, [None] * N
+            self._dsz = ctypes.sizeof(DepthParams)
+            self._depth_host = (DepthParams * N)()
+            self._depth_tab = z(N * self._dsz, dt=torch.uint8)
+            self._depth_enable = z(N, dt=torch.uint8)
+            self._depth_work = z(N, DEPTH_WORK_BYTES, dt=torch.uint8)
         self._readback = [self.state.view(-1), self.search_crop[:, 0, 2]]  # what a step returns to the host
         self._graph = self._plan = self._rt = self._ws = self._ws_tl = None
         self.last_scores = None  # online-score tracker: every slot's sigmoid(score) of the last step
@@ -508,30 +611,56 @@ class RGBTBatchTrackerCore:
         for host, tab in ((self._search_host, self._search_tab), (self._tmpl_host, self._tmpl_tab)):
             tab[lo:hi].copy_(torch.frombuffer(host, dtype=torch.uint8)[lo:hi])
         self.hw[b].copy_(torch.tensor([H, W], dtype=torch.int32))
+        if self.aux_format == "depth16":
+            self._dview[b] = self._dbuf[b][:H * W].view(H, W)
+            self._depth_host[b] = depth_params(self._dview[b], self._fview[b][1], self._depth_work[b])
+            lo, hi = b * self._dsz, (b + 1) * self._dsz
+            self._depth_tab[lo:hi].copy_(torch.frombuffer(self._depth_host, dtype=torch.uint8)[lo:hi])
 
     def _load_frames(self, b, image):
         """Copy slot b's two (H, W, 3) uint8 frames (numpy or torch) into its device buffers; a new
-        frame size grows the buffers if needed and rewrites the slot's table entries."""
-        if not isinstance(image, (list, tuple)) or len(image) != 2:
-            raise ValueError("image must be [image_v, image_i]")
-        ims = [torch.as_tensor(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x for x in image]
-        H, W = ims[0].shape[:2]
-        if any(tuple(x.shape) != (H, W, 3) or x.dtype != torch.uint8 for x in ims) or H <= 0 or W <= 0:
-            raise ValueError("frames must be two (H, W, 3) uint8 images of the same size")
+        frame size grows the buffers if needed and rewrites the slot's table entries.  aux_format="depth16":
+        the second frame is the raw (H, W) depth frame, copied into the slot's depth buffer; the step graph (or
+        `assign`) prepares it into the second frame buffer."""
+        depth = None
+        if self.aux_format == "depth16":
+            H, W, rgb, depth = _split_pair(image)
+            ims = [rgb]
+        else:
+            if not isinstance(image, (list, tuple)) or len(image) != 2:
+                raise ValueError("image must be [image_v, image_i]")
+            ims = [torch.as_tensor(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x for x in image]
+            H, W = ims[0].shape[:2]
+            if any(tuple(x.shape) != (H, W, 3) or x.dtype != torch.uint8 for x in ims) or H <= 0 or W <= 0:
+                raise ValueError("frames must be two (H, W, 3) uint8 images of the same size")
         if self.frames[b] is None or self.frames[b][0].numel() < H * W * 3:
             self.frames[b] = [torch.empty(H * W * 3, device=self.dev, dtype=torch.uint8) for _ in range(2)]
+            if depth is not None:
+                self._dbuf[b] = torch.empty(H * W, device=self.dev, dtype=torch.int16)
             self._hw[b] = (0, 0)
         if self._hw[b] != (H, W):
             self._hw[b] = (H, W)
             self._write_entries(b)
         for dst, src in zip(self._fview[b], ims):
             dst.copy_(src, non_blocking=src.device.type == "cuda")
+        if depth is not None:
+            self._dview[b].copy_(depth, non_blocking=depth.device.type == "cuda")
 
     def _set_active(self, b, on):
         self._active[b] = bool(on)
         self._act = [i for i in range(self.slots) if self._active[i]]
         self.active[b] = int(on)
         self._search_enable[2 * b:2 * b + 2] = int(on)
+        if self.aux_format == "depth16":
+            self._depth_enable[b] = int(on)
+
+    def _depth_node(self):
+        """aux_format="depth16": the first launches of every step, full or packed: the active slots' depth frames
+        prepared into their second frame buffers (an inactive slot's entry is disabled: nothing of it is written)."""
+        if self.aux_format != "depth16":
+            return []
+        return [(LIB.mmt_depth_prepare_table, (self._depth_tab.data_ptr(), self._depth_enable.data_ptr(), self.slots),
+                 "track_depth_prepare_table", None)]
 
     def _crop_templates(self, slots):
         """One table launch: both modalities' template crops of `slots`, each at its slot's state."""
@@ -558,8 +687,9 @@ class RGBTBatchTrackerCore:
             model_plan = rt.plan_for_inputs(self.template, self.online_template, self.search,
                                             run_score_head=self.online_score)
         ws = self._ws = rt.workspace(N)
-        plan = [(LIB.mmt_sample_target_table, (self._search_tab.data_ptr(), self._search_enable.data_ptr(), 2 * N, self.ss),
-                 "track_sample_target_table", None)]
+        plan = self._depth_node()
+        plan.append((LIB.mmt_sample_target_table, (self._search_tab.data_ptr(), self._search_enable.data_ptr(), 2 * N, self.ss),
+                     "track_sample_target_table", None))
         plan += model_plan
         plan.append((LIB.mmt_track_update_slots, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), 8, self.state.data_ptr(),
                                                   self.hw.data_ptr(), self.active.data_ptr(), N, self.ss, 10.0),
@@ -592,9 +722,10 @@ class RGBTBatchTrackerCore:
             model_plan = rt.plan_for_inputs(pk["template"], pk["online_template"], search,
                                             run_score_head=self.online_score, ws_key=key)
         row = 3 * self.ss * self.ss
-        plan = [(LIB.mmt_sample_target_packed, (self._search_tab.data_ptr(), self._search_enable.data_ptr(),
-                                                pk["list"].data_ptr(), R, N, 2, self.ss, pk["search"].data_ptr(), R * row, row),
-                 "track_sample_target_packed", None)]
+        plan = self._depth_node()
+        plan.append((LIB.mmt_sample_target_packed, (self._search_tab.data_ptr(), self._search_enable.data_ptr(),
+                                                    pk["list"].data_ptr(), R, N, 2, self.ss, pk["search"].data_ptr(), R * row, row),
+                     "track_sample_target_packed", None))
         plan += gather
         plan += model_plan
         plan.append((LIB.mmt_track_update_packed, (ws["BOX"].data_ptr(), self.search_crop.data_ptr(), 8, self.state.data_ptr(),
@@ -658,6 +789,9 @@ class RGBTBatchTrackerCore:
         if not 0 <= b < self.slots:
             raise IndexError("slot %d of %d" % (b, self.slots))
         self._load_frames(b, image)
+        if self.aux_format == "depth16":  # eagerly, before the template crop reads the frame
+            check(LIB.mmt_depth_prepare(ctypes.byref(self._depth_host[b]), 1, torch.cuda.current_stream().cuda_stream),
+                  "mmt_depth_prepare")
         self.state[b].copy_(torch.tensor([float(v) for v in init_bbox], dtype=torch.float64))
         self._crop_templates([b])
         for m in range(2):
