@@ -57,6 +57,9 @@
  *       batched tracker): crop descriptors in a device table, per-slot frame size and active mask
  *   mmt_sample_target_packed / mmt_track_update_packed  the same two indexed by a slot list in device
  *       memory (the batched tracker's packed step: the model runs at a smaller batch on the active slots only)
+ *   mmt_train_crops_table       the training input's pixel passes, lib/train/data/processing_rgbt.py:143-228 with
+ *       the transforms of lib/train/base_functions.py:177-183 (joint grayscale / flip, crop, brightness jitter,
+ *       colour map, flip, normalise, attention mask), crop descriptors in a device table
  *   mmt_slot_copy               no reference counterpart: moves the rows of listed tracker slots between a
  *       compact staging layout and the N-slot layout (the batched tracker's per-slot template K/V cache:
  *       template crops in, per-layer K / V columns out), slot lists and segments in device memory
@@ -693,6 +696,50 @@ typedef struct {
 } mmt_depth_params;
 int mmt_depth_prepare(const mmt_depth_params* p, int n, void* stream);
 int mmt_depth_prepare_table(const mmt_depth_params* table_dev, const uint8_t* enable_dev, int n, void* stream);
+
+/* ---------------------------------------------------------------- training input
+ * mmt_train_crops_table: the pixel passes of the reference's training-side MixformerProcessing
+ * (lib/train/data/processing_rgbt.py:143-228, transforms of lib/train/base_functions.py:177-183) for n
+ * crops of equal out_sz in one launch, from a descriptor table in DEVICE memory as
+ * mmt_sample_target_table (a captured graph holds only the two pointers).  Per entry:
+ *   joint stage   src_gray: cvtColor(COLOR_RGB2GRAY), (R*4899 + G*9617 + B*1868 + 8192) >> 14, replicated
+ *                 to three channels; src_flip: np.fliplr.  Both are applied to the source taps: `image` is
+ *                 the frame as stored, column ix of the mirrored frame is stored column W - 1 - ix, and
+ *                 `box` is given in the mirrored frame's coordinates.
+ *   crop          sample_target(frame, box, factor, out_sz) with mmt_sample_target's geometry, padding
+ *                 (the dropped last column / row is the mirrored frame's) and resize, bit for bit.
+ *   jitter        lut NULL (RGB): x = float(v) * (float)gain, gain = brightness_factor / 255.0;
+ *                 lut set (TIR): v' = trunc(min(double(v) * gain, 255)), gain = tir_factor, then the colour
+ *                 map BGR2GRAY + lut[gray][c], then x = float(v') / 255.0f (a true division).
+ *   normalise     out = (min(max(x, 0), 1) - mean) / std, [3][out_sz][out_sz] fp32.
+ *   att           [out_sz][out_sz] bytes 0 / 1: cv2.resize (float path: the taps of the 8-bit path with
+ *                 float weights 1 - f, f; the 4-pixel average at an exact 2x) of the mask that is 1 on
+ *                 padding, != 0.
+ *   out_flip      pixel dx is written to column out_sz - 1 - dx of out, att and patch.
+ * Optional outputs (NULL: not written): out, att, patch [out_sz][out_sz][3] uint8 (the resized crop before the
+ * jitter), crop [4] fp64 = (x1, y1, crop_sz, out_sz / crop_sz).  A crop_sz < 1 gives zero pixels and att 1.
+ * mmt_amd/train_input.py restates the whole per-sample pipeline on the host, bit for bit.
+ * An entry is SKIPPED -- nothing is written for it -- when its enable byte is 0, image or box is NULL,
+ * out, att and patch are all NULL, H <= 0 or W <= 0, factor is not > 0, its out_sz differs from the launch's, or
+ * gain is not finite and >= 0.  MMT_EBADARG (before any launch): table_dev NULL or not 8-byte aligned, n <= 0,
+ * out_sz <= 0 or > 16384, or n * ceil(out_sz^2 / 256) blocks past the grid limit 2^31 - 1. */
+typedef struct {
+    const uint8_t* image; /* [H][W][3] uint8, as stored (not mirrored) */
+    int32_t H, W;
+    const double* box;    /* [4] x, y, w, h: the jittered box in the joint-flipped frame's coordinates */
+    double factor;
+    int32_t out_sz;
+    const uint8_t* lut;   /* NULL: the RGB arithmetic; [256][3]: the TIR arithmetic */
+    float mean[3], std[3];
+    double gain;          /* RGB: bf / 255.0 (rounded to float in the kernel); TIR: tf */
+    uint8_t src_flip, src_gray, out_flip;
+    float* out;
+    uint8_t* att;
+    uint8_t* patch;
+    double* crop;
+} mmt_train_crop_params;
+int mmt_train_crops_table(const mmt_train_crop_params* table_dev, const uint8_t* enable_dev, int n, int out_sz,
+                          void* stream);
 
 /* Slot-indexed row copy (the batched tracker's per-slot template K/V cache).  A segment describes one
  * strided 2-D block per slot on each side: slot s, row r occupies row_bytes bytes at

@@ -27,7 +27,7 @@
 // the edges taken with weight 2048) and its exact-2x INTER_AREA shortcut ((a+b+c+d+2)>>2); the
 // colour map is cvtColor(BGR2GRAY) fixed point (1868, 9617, 4899, >>14) then a 256x3 LUT passed in.
 // The oracle (oracle/preprocess.py) restates the same arithmetic; both are bit-exact to each other.
-#include "common.hpp"
+#include "crop_common.hpp"  // the crop geometry, the resize and the colour map, shared with train_input.hip
 
 // Parity is bit-exact against separately rounded torch / numpy / Python ops: no FMA contraction.
 #pragma clang fp contract(off)
@@ -38,39 +38,14 @@ struct CropBatch {
     mmt_crop_params c[MMT_MAX_CROPS];
 };
 
-// Python's int(round(v)) for the crop corner: round half to even.
-MMT_DEV int py_round(double v) { return (int)rint(v); }
+MMT_DEV Geo crop_geometry(const mmt_crop_params& p) { return ::crop_geometry(p.box, p.factor, p.H, p.W); }
 
-MMT_DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-MMT_DEV short coef(float v) {  // saturate_cast<short>(v * INTER_RESIZE_COEF_SCALE): cvRound
-    const int r = (int)rintf(v * 2048.f);
-    return (short)clampi(r, -32768, 32767);
-}
-
-struct Geo {
-    int x1, y1, crop, xlim, ylim;  // padded-crop origin, size, and the first image column/row not copied
-};
-
-MMT_DEV Geo crop_geometry(const mmt_crop_params& p) {
-    const double x = p.box[0], y = p.box[1], w = p.box[2], h = p.box[3];
-    Geo g;
-    g.crop = (int)ceil(sqrt(w * h) * p.factor);
-    g.x1 = py_round(x + 0.5 * w - g.crop * 0.5);
-    g.y1 = py_round(y + 0.5 * h - g.crop * 0.5);
-    // im[y1+y1_pad : y2-y2_pad, x1+x1_pad : x2-x2_pad] with x2_pad = max(x2 - W + 1, 0): when the crop
-    // runs past the right (bottom) edge, the last image column (row) is not copied either.
-    const int x2 = g.x1 + g.crop, y2 = g.y1 + g.crop;
-    g.xlim = x2 >= p.W ? p.W - 1 : p.W;
-    g.ylim = y2 >= p.H ? p.H - 1 : p.H;
-    return g;
-}
-
-// padded crop pixel (row r, col c) channel ch: image pixel or the constant border 0
-MMT_DEV int src_px(const mmt_crop_params& p, const Geo& g, int r, int c, int ch) {
+// padded crop pixel (row r, col c), three channels: image pixel or the constant border 0
+MMT_DEV Px3 src_px(const mmt_crop_params& p, const Geo& g, int r, int c) {
     const int iy = g.y1 + r, ix = g.x1 + c;
-    if (iy < 0 || ix < 0 || iy >= g.ylim || ix >= g.xlim) return 0;
-    return p.image[((int64_t)iy * p.W + ix) * 3 + ch];
+    if (iy < 0 || ix < 0 || iy >= g.ylim || ix >= g.xlim) return Px3{{0, 0, 0}};
+    const uint8_t* q = p.image + ((int64_t)iy * p.W + ix) * 3;
+    return Px3{{q[0], q[1], q[2]}};
 }
 
 // One output pixel (idx = dy * out_sz + dx) of crop p with geometry g: resize, optional colour map,
@@ -85,46 +60,14 @@ MMT_DEV void sample_pixel(const mmt_crop_params& p, const Geo& g, int idx) {
         p.crop[2] = g.crop;
         p.crop[3] = (double)os / g.crop;  // resize_factor = output_sz / crop_sz
     }
-    int v[3] = {0, 0, 0};
-    if (g.crop >= 1) {
-        const double inv = (double)os / g.crop, scale = 1.0 / inv;
-        const int is = (int)rint(scale);
-        if (is == 2 && fabs(scale - is) < 2.220446049250313e-16) {  // INTER_LINEAR at exactly 1/2 -> INTER_AREA
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                v[ch] = (src_px(p, g, 2 * dy, 2 * dx, ch) + src_px(p, g, 2 * dy, 2 * dx + 1, ch) +
-                         src_px(p, g, 2 * dy + 1, 2 * dx, ch) + src_px(p, g, 2 * dy + 1, 2 * dx + 1, ch) + 2) >> 2;
-        } else {
-            float fx = (float)((dx + 0.5) * scale - 0.5);
-            int sx = (int)floorf(fx);
-            fx -= sx;
-            if (sx < 0) fx = 0.f, sx = 0;
-            if (sx >= g.crop - 1) fx = 0.f, sx = g.crop - 1;
-            float fy = (float)((dy + 0.5) * scale - 0.5);
-            const int sy = (int)floorf(fy);
-            fy -= sy;
-            const int a0 = coef(1.f - fx), a1 = coef(fx), b0 = coef(1.f - fy), b1 = coef(fy);
-            const int r0 = clampi(sy, 0, g.crop - 1), r1 = clampi(sy + 1, 0, g.crop - 1);
-            const int sx1 = min(sx + 1, g.crop - 1);  // weight a1 is 0 whenever sx + 1 is past the edge
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int h0 = src_px(p, g, r0, sx, ch) * a0 + src_px(p, g, r0, sx1, ch) * a1;
-                const int h1 = src_px(p, g, r1, sx, ch) * a0 + src_px(p, g, r1, sx1, ch) * a1;
-                const int t = (((h0 >> 4) * b0) >> 16) + (((h1 >> 4) * b1) >> 16);
-                v[ch] = clampi((t + 2) >> 2, 0, 255);
-            }
-        }
-    }
+    int v[3];
+    resize_pixel([&](int r, int c) { return src_px(p, g, r, c); }, g.crop, os, dy, dx, v);
     const int64_t o = (int64_t)dy * os + dx;
     if (p.patch) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) p.patch[o * 3 + ch] = (uint8_t)v[ch];
     }
-    if (p.lut) {  // cv2.applyColorMap on a 3-channel crop: BGR2GRAY, GRAY2BGR, per-channel LUT
-        const int gray = (v[0] * 1868 + v[1] * 9617 + v[2] * 4899 + (1 << 13)) >> 14;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) v[ch] = p.lut[gray * 3 + ch];
-    }
+    if (p.lut) colour_map(p.lut, v);
     if (p.out) {
         const float inv255 = 1.0f / 255.0f;  // torch: tensor / python scalar = tensor * (1 / scalar)
 #pragma unroll

@@ -79,6 +79,14 @@ class DepthParams(ctypes.Structure):
     _fields_ = [("depth", vp), ("H", i32), ("W", i32), ("out", vp), ("work", vp), ("record", vp)]
 
 
+class TrainCropParams(ctypes.Structure):
+    """mmt_train_crop_params."""
+    _fields_ = [("image", vp), ("H", i32), ("W", i32), ("box", vp), ("factor", f64), ("out_sz", i32),
+                ("lut", vp), ("mean", f32 * 3), ("std", f32 * 3), ("gain", f64),
+                ("src_flip", ctypes.c_uint8), ("src_gray", ctypes.c_uint8), ("out_flip", ctypes.c_uint8),
+                ("out", vp), ("att", vp), ("patch", vp), ("crop", vp)]
+
+
 class ConvWprep(ctypes.Structure):
     _fields_ = [("w", vp), ("b", vp), ("wf", vp), ("wb", vp), ("bp", vp), ("cout", i32), ("cp", i32), ("cin", i32),
                 ("pad_", i32)]
@@ -171,6 +179,7 @@ _PROTOS = {
     "mmt_track_update_packed": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f64, vp],
     "mmt_depth_prepare": [ctypes.POINTER(DepthParams), i32, vp],
     "mmt_depth_prepare_table": [vp, vp, i32, vp],
+    "mmt_train_crops_table": [vp, vp, i32, i32, vp],
     "mmt_slot_copy": [vp, i32, vp, i32, vp, i32, i32, i64, vp],
     "mmt_adamw_chunk_elems": [],
     "mmt_adamw_step": [vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f32, i32, vp],

@@ -24,6 +24,8 @@ ones carry `register_autograd` formulas built from the registered backward ops:
                                                 row gather is the row gather by the inverted index
   mmt::depth_prepare                            mmt_depth_prepare: a raw 16-bit depth frame clipped, normalised
                                                 and replicated into the tracker's (H, W, 3) uint8 frame
+  mmt::train_crops                              mmt_train_crops_table: the training input's jittered crops, flips,
+                                                brightness jitter and normalise from a device descriptor table
 
 Each *_forward op has its backward registered (register_autograd over the *_backward ops), so
 autograd, FakeTensor and torch.compile see one op per native call.
@@ -448,6 +450,38 @@ def depth_prepare(depth: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 def _(depth):
     H, W = depth.shape
     return depth.new_empty(H, W, 3, dtype=torch.uint8), depth.new_empty(7, dtype=torch.int32)
+
+
+# ------------------------------------------------------------------------------------------- training input
+@torch.library.custom_op("mmt::train_crops", mutates_args=("images_v", "images_i", "att_v", "att_i", "crop"))
+def train_crops(table: torch.Tensor, enable: Optional[torch.Tensor], out_sz: int, images_v: torch.Tensor,
+                images_i: torch.Tensor, att_v: torch.Tensor, att_i: torch.Tensor, crop: torch.Tensor) -> None:
+    """mmt_train_crops_table over a device table of mmt_train_crop_params (a uint8 tensor, one entry per
+    sizeof(mmt_train_crop_params) bytes), enable: None or one byte per entry.  The entries' out / att pointers lie
+    inside images_v / images_i (fp32) and att_v / att_i (uint8), their crop records inside crop (fp64), and their
+    patch pointers are NULL: the five tensors are all this op may write
+    (mmt_amd.train_input.TrainInputProcessor owns both; process_sample_reference is the host restatement)."""
+    from ._lib import TrainCropParams
+    import ctypes
+    _need(table, "table", (torch.uint8,))
+    size = ctypes.sizeof(TrainCropParams)
+    if table.dim() != 1 or table.numel() == 0 or table.numel() % size:
+        raise RuntimeError("train_crops: table must hold a whole number (>= 1) of %d-byte entries" % size)
+    n = table.numel() // size
+    if enable is not None:
+        _need(enable, "enable", (torch.uint8,))
+        if enable.numel() != n:
+            raise RuntimeError("train_crops: enable must hold one byte per entry (%d), got %d" % (n, enable.numel()))
+    for t, name, dt in ((images_v, "images_v", torch.float32), (images_i, "images_i", torch.float32),
+                        (att_v, "att_v", torch.uint8), (att_i, "att_i", torch.uint8), (crop, "crop", torch.float64)):
+        _need(t, name, (dt,))
+    check(LIB.mmt_train_crops_table(table.data_ptr(), enable.data_ptr() if enable is not None else None, n, out_sz,
+                                    torch.cuda.current_stream().cuda_stream), "mmt_train_crops_table")
+
+
+@train_crops.register_fake
+def _(table, enable, out_sz, images_v, images_i, att_v, att_i, crop):
+    return None
 
 
 def mam_attention(qkv, n_t, heads):
